@@ -14,8 +14,8 @@ MI355X". Workloads (--workload):
   (final_project/v4_mpi_cuda/src/main_mpi_cuda.cpp:52-130) — run by the native V4 runtime
   (anx/v4.hpp): the batch lives in one shared pinned host segment, every rank DMAs its own images x
   input rows (halo included) over its own host link and its output rows back, in image chunks so
-  H2D, compute and D2H overlap. The JSON reports the H2D GB/s in the step and the link's H2D-only
-  rate (``h2d_bound_img_s``: what the H2D stage alone would allow).
+  H2D, compute and D2H overlap. The JSON reports the H2D GB/s in the step and, with ``--full``, the
+  link's H2D-only rate (``h2d_bound_img_s``: what the H2D stage alone would allow).
 * ``v5``: BASELINE config "V5 GPU-aware, batch 1024", device-resident "halo + gather": with
   ``--input-source local`` (default) every rank's images x input rows are placed on its device once,
   so a step moves only the per-layer pool1 halos of a row group and the gather (``root``: the
@@ -27,22 +27,31 @@ MI355X". Workloads (--workload):
   reference's row split over every rank) | hybrid (batch first, rows only below one image per rank) |
   batch.
 
-Every workload's JSON carries a top-level ``model_curve``: the MODELLED 1/2/4/8-GPU curve of its
+A plain run (``bench.py --gpus 1 --steps N --warmup W``) does what the headline needs and no more: it
+sets up, settles the clock and warms up, times the N steps, writes the last timed step's output when
+``--dump-outputs DIR`` is given, and prints the record (``vs_baseline`` is null there). Everything else
+below is measured or checked only with ``--full``.
+
+``--full``: every workload's JSON carries a top-level ``model_curve``: the MODELLED 1/2/4/8-GPU curve of its
 configuration (``"measured": false``; anx.parallel.cost), with this run's measured single-GPU rate in the
 model's throughput table when N = 1. It is kept out of ``config`` so no modelled number sits among the
 measured ones.
 
-The dp run also carries ``v4`` and ``v5``: BASELINE configs 3 and 4 (the reference's multi-GPU programs)
-measured on the same ranks by the native runtimes, V5 with and without the pool1 halo exchange
-(:func:`reference_programs`; ``--no-ref-programs`` skips them).
+``--full``: the dp run also carries ``v4`` and ``v5``: BASELINE configs 3 and 4 (the reference's multi-GPU
+programs) measured on the same ranks by the native runtimes, V5 with and without the pool1 halo exchange
+(:func:`reference_programs`; ``--no-ref-programs`` skips them), the bf16 full-AlexNet extension
+(``full_bf16``; ``--no-full`` skips it) and, at N > 1, the gather verification step (``--no-verify``); the v5
+workload its forced-halo sub-records, the v4 workload its H2D link probe.
 
 Launch: ``python bench.py`` (1 GPU) or ``python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N``. Rank 0 prints ONE JSON line.
 
 Inputs: the dp workload streams ``input_batches_rotated`` distinct synthetic batches (>= 4 and
-> 256 MB together, more than the 256 MB Infinity Cache) round-robin through the timed steps.
+> 256 MB together, more than the 256 MB Infinity Cache) round-robin through the timed steps. All inputs
+come from seeded generators and the first warmup step always reads batch 0, so the same arguments give the
+same inputs, step for step, in every run.
 
-The reference's own configuration, one image (batch 1) through H2D + forward + D2H, is measured
+``--full``: the reference's own configuration, one image (batch 1) through H2D + forward + D2H, is measured
 three ways: ``b1_process_cold_ms`` = a fresh ``anx --version v3`` process (context creation,
 allocation, weight upload, copies: what the reference's 610.661 ms timed) started
 before this process touches the GPU; ``b1_engine_cold_ms`` = a fresh engine on this already
@@ -88,6 +97,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the batch-1 cold / warm probes "
+                         "(vs_baseline), the native V4 / V5 programs, the V5 halo sub-records, the bf16 extension, the "
+                         "V4 link probe, the modelled curve and the N>1 gather verification (the --no-* switches "
+                         "below drop single ones). Off: set up, warm up, time --steps steps, print the record")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0: the arrays a "
+                         "caller of the step receives) as DIR/<name>.npy, float32, at most 64 MB in all (a seeded "
+                         "sample of a larger array)")
     ap.add_argument("--workload", default="dp", choices=["dp", "v4", "v5"])
     ap.add_argument("--batch-per-gpu", type=int, default=None,
                     help="dp: images per GPU (default 128 for blocks; 256 for full = BASELINE's 2048 over 8 GPUs)")
@@ -502,6 +520,29 @@ def _oracle(model):
     return check
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: all arrays together stay below 64 MB
+
+
+def dump_outputs(dirname: str, arrays: dict) -> dict:
+    """Write each tensor as ``dirname/<name>.npy`` (float32; float64 stays). An array beyond its share of
+    DUMP_BYTES is written as a fixed sample: the flat elements at sorted indices drawn once from seed 0, so
+    two runs (or two builds) sample the same elements."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    desc = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        arr = (t if t.dtype == torch.float64 else t.float()).contiguous().numpy()
+        shape = list(arr.shape)
+        if arr.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(arr.size, share // arr.itemsize, replace=False))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        desc[name] = {"shape": shape, "written": list(arr.shape), "dtype": str(arr.dtype)}
+    return desc
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -510,7 +551,7 @@ def main():
     if world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}")
     # before this process's first GPU call (a child of a GPU-initialised process would not be cold)
-    b1p = process_cold_b1(a.cold_gap_s, a.cold_trials) if (rank == 0 and a.device == "cuda" and not a.no_b1 and a.model == "blocks") else {}
+    b1p = process_cold_b1(a.cold_gap_s, a.cold_trials) if (a.full and rank == 0 and a.device == "cuda" and not a.no_b1 and a.model == "blocks") else {}
     from anx.parallel import selfcheck
     ident = None
     with selfcheck.FirstCollectiveWatchdog(rank, a.first_collective_s if world > 1 else 0,
@@ -657,6 +698,13 @@ def main():
             step()
         sync()
     prewarm_ms = round((time.perf_counter() - t_pw) * 1e3, 1)
+    if wl is None and pipe.inputs:
+        # The prewarm's step count follows the clock, so it leaves the round-robin at a different batch in
+        # every run: rotate the list so that the first warmup step reads batch 0, and the timed steps (and
+        # --dump-outputs) see the same batches in the same order from run to run.
+        k0 = pipe._k % len(pipe.inputs)
+        if k0:
+            pipe.inputs = pipe.inputs[-k0:] + pipe.inputs[:-k0]
 
     for _ in range(a.warmup):
         step()
@@ -686,9 +734,23 @@ def main():
     per_step = B if wl is not None else B * (world - 1) + root_b  # images per step over the whole job
     imgs = per_step * a.steps / el
     phases = wl.phase_ms() if wl is not None else None
-    # N > 1: one more (untimed) step, then prove the gather and the numerics (selfcheck.verify_gather)
+    dumped = None
+    if a.dump_outputs:  # the last timed step's output, as its caller gets it (rank 0 holds the gathered one)
+        if wl is not None:
+            wl.sync()
+            y_last = wl.output()
+        else:
+            pipe.drain()
+            sync()
+            if pipe.y_global is None:
+                y_last = pipe.y
+            else:  # rank 0's own share (rows past it are unused when it sheds), then every peer's
+                y_last = torch.cat([pipe.y_global[0, :root_b], pipe.y_global[1:].flatten(0, 1)])
+        if rank == 0 and y_last is not None:
+            dumped = dump_outputs(a.dump_outputs, {"output": y_last})
+    # --full, N > 1: one more (untimed) step, then prove the gather and the numerics (selfcheck.verify_gather)
     verify = None
-    if wl is None and world > 1 and not a.no_verify and a.model == "blocks":
+    if a.full and wl is None and world > 1 and not a.no_verify and a.model == "blocks":
         step()
         pipe.drain()
         sync()
@@ -710,6 +772,8 @@ def main():
                            "lane_sync": ("free-running lanes, staggered at a mid-forward event (forward_async)" if pipe.async_lanes
                                          else "lanes forked/joined every step" if a.full_lanes > 1 else "one lane")},
             }
+            if dumped is not None:
+                rec["dumped_outputs"] = dumped
             print(json.dumps(rec), flush=True)
         if world > 1:
             dist.barrier()
@@ -754,7 +818,10 @@ def main():
                         "stage1 (chunks) -> pool1 halo chunks -> stage2 (halo-free ranks: free-running lanes) -> "
                         "gather (native V5 runtime; gather on a second stream under the next step)")
             extra = {**wl.describe(), "workload": a.workload, "decomp": a.decomp, "phases_ms": phases}
-            if a.workload == "v4" and cuda:
+            if a.workload == "v4" and cuda and not a.full:  # the step's own H2D rate; the link probe is --full's
+                extra["h2d_gbps_in_step"] = (round(extra["h2d_bytes_per_step_rank"] / (phases["h2d"] * 1e6), 2)
+                                             if phases.get("h2d") else None)
+            elif a.workload == "v4" and cuda:
                 gbps = wl.probe_h2d_gbps()
                 per_img = extra["h2d_bytes_per_step_rank"] / max(1, -(-GB // world))
                 extra.update({"h2d_gbps_link": round(gbps, 2),
@@ -767,7 +834,7 @@ def main():
         # the modelled 1/2/4/8-GPU curve of this configuration (anx/cost.hpp; measured: false), with
         # this run's measured rate in the throughput table when it ran on one GPU
         model = None
-        if cuda:
+        if cuda and a.full:
             from anx.parallel import cost
             wl_name = "dp" if wl is None else a.workload
             per_gpu = B if wl is None else GB
@@ -827,29 +894,32 @@ def main():
                 rec["verify"] = verify
         if model is not None:  # modelled, not measured: outside the measured config
             rec["model_curve"] = {"measured": False, **model}
+        if dumped is not None:
+            rec["dumped_outputs"] = dumped
 
     # Secondary records, after the headline is measured and its record built. Their native multi-GPU
     # programs (V4 / V5 over RCCL and peer IPC) meet real multi-GPU hardware for the first time in the
     # driver's N > 1 runs: a hung call there must not take the headline line with it (SecondaryDeadline).
+    # All of them belong to --full: a plain run goes straight to the closing barrier and prints the headline.
     t_sec = time.perf_counter()
     guard = selfcheck.SecondaryDeadline(rank, a.secondary_deadline_s, rec,
-                                        hang=os.environ.get("ANX_BENCH_HANG_STAGE"))  # hang: tests only
+                                        hang=os.environ.get("ANX_BENCH_HANG_STAGE") if a.full else None)  # hang: tests only
     guard.stage("v5_subrecords")
     subs = {}
-    if cuda and wl is not None and a.workload == "v5" and not a.no_subrecords:
+    if a.full and cuda and wl is not None and a.workload == "v5" and not a.no_subrecords:
         subs = v5_halo_subrecords(a, world, rank, GB, dev, g)
     guard.stage("batch1")
-    b1 = batch1_latency(dev) if (rank == 0 and cuda and not a.no_b1) else {}
+    b1 = batch1_latency(dev) if (a.full and rank == 0 and cuda and not a.no_b1) else {}
     guard.stage("reference_programs")
     refs = None
-    if wl is None and a.model == "blocks" and not a.no_ref_programs:
+    if a.full and wl is None and a.model == "blocks" and not a.no_ref_programs:
         try:
             refs = reference_programs(a, world, rank, dev, cuda, g)
         except Exception as e:
             refs = {"error": repr(e)[:300]}
     guard.stage("full_bf16")
     full = None
-    if cuda and wl is None and not a.no_full:
+    if a.full and cuda and wl is None and not a.no_full:
         try:
             full = full_bf16_secondary(dev, world, rank)
         except Exception as e:  # the headline record must not depend on the extension
@@ -862,7 +932,8 @@ def main():
         if refs is not None:
             rec.update(refs) if "error" not in refs else rec.update({"reference_programs_error": refs["error"]})
         rec.update(subs)
-        rec["secondary_s"] = round(time.perf_counter() - t_sec, 1)
+        if a.full:
+            rec["secondary_s"] = round(time.perf_counter() - t_sec, 1)
         guard.emit(rec)
     if world > 1:
         dist.barrier()

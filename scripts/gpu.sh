@@ -52,7 +52,7 @@ for s in "$@"; do
   case $s in
     tests) run tests 900 python -u -m pytest tests -x -v -m gpu --timeout 170 --timeout-method thread ;;
     smoke) run smoke 300 python __graft_entry__.py smoke ;;
-    bench) run bench 300 python bench.py --steps 20 --warmup 5 $BARGS ;;
+    bench) run bench 300 python bench.py --full --steps 20 --warmup 5 $BARGS ;;
     sweep) run sweep 600 python tools/sweep_batch.py --batches ${SWEEP:-64,128,256,300,600} --rounds 3 --iters 10 \
              ${SWEEP_ARGS:-} ;;
     ab) run ab 900 python tools/ab_variants.py --arms "${AB_ARMS:-|conv1_occ=3}" --batch "${AB_BATCH:-300}" \
@@ -72,9 +72,9 @@ for s in "$@"; do
       run matrix_b256 600 bash scripts/run_matrix.sh --no-build --batch 256 --iters 1 --out "$O/matrix" ;;
     peak) run peak 120 bash -c "$B/anx_mfmapeak --waves 1 && $B/anx_mfmapeak --waves 2 && $B/anx_mfmapeak --waves 4" ;;
     workloads)
-      run wl_v4 300 python bench.py --workload v4 --steps 10 --warmup 3
-      run wl_v5 300 python bench.py --workload v5 --steps 10 --warmup 3
-      run wl_v5_root 300 python bench.py --workload v5 --input-source root --steps 10 --warmup 3 --no-b1 ;;
+      run wl_v4 300 python bench.py --full --workload v4 --steps 10 --warmup 3
+      run wl_v5 300 python bench.py --full --workload v5 --steps 10 --warmup 3
+      run wl_v5_root 300 python bench.py --full --workload v5 --input-source root --steps 10 --warmup 3 --no-b1 ;;
     ingest) run probe_ingest 600 python tools/probe_ingest.py ${INGEST_ARGS:-} ;;
     versions)
       run v3_b1 120 $B/anx --version v3 --iters 20 --check

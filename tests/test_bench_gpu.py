@@ -27,7 +27,7 @@ def bench(args):
 def test_bench_blocks_contract():
     with open(os.path.join(ROOT, "BASELINE.json")) as f:
         metric = json.load(f)["metric"]
-    rec = bench(["--batch-per-gpu", "64"])
+    rec = bench(["--full", "--batch-per-gpu", "64"])
     c = rec["config"]
     assert rec["metric"] == metric and rec["dtype"] == "fp32" and c["global_batch"] == 64
     assert c["lanes"] == 2 and rec["vs_baseline"] > 1 and c["b1_warm_ms"] > 0
@@ -56,9 +56,41 @@ def test_bench_blocks_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_headline_only_and_dump(tmp_path):
+    """A plain run times the headline and nothing else (no batch-1 probes, no secondary programs, no
+    modelled curve), and --dump-outputs writes the last timed step's output: warmup 1 + 3 steps read the
+    seeded batches 0..3 whatever the prewarm did, so batch 3 through the fp64 oracle must match it."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    from anx.config import blocks
+    from anx.models.reference import blocks_forward_all
+    from anx.utils.init import init_weights
+    rec = bench(["--batch-per-gpu", "64", "--dump-outputs", str(tmp_path)])
+    c = rec["config"]
+    assert rec["dtype"] == "fp32" and rec["ms_per_step"] > 0 and c["global_batch"] == 64 and c["lanes"] == 2
+    assert rec["vs_baseline"] is None and not any(k.startswith("b1_") for k in c)
+    assert not any(k in rec for k in ("v4", "v5", "full_bf16", "model_curve", "secondary_s"))
+    assert abs(rec["value"] - 64 * 1e3 / rec["ms_per_step"]) < 1e-3 * rec["value"]
+    y = np.load(tmp_path / "output.npy")
+    assert y.dtype == np.float32 and y.shape == (64, 13, 13, 256) and np.isfinite(y).all()
+    assert rec["dumped_outputs"]["output"]["written"] == [64, 13, 13, 256]
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    assert c["input_batches_rotated"] == 8
+    xs = [torch.rand((64, 227, 227, 3), device=dev, generator=g) * 0.1 for _ in range(1 + 4)]  # buffer, batches 0..3
+    b1, b2 = blocks()
+    pick = [0, 31, 32, 63]  # both lanes' first and last image
+    ref = blocks_forward_all(xs[4][pick].cpu(), init_weights("rand", 1234, b1, b2), b1, b2, device=dev)
+    err = (torch.from_numpy(y[pick]).double() - ref).abs().amax(dim=(1, 2, 3)) / ref.abs().amax(dim=(1, 2, 3))
+    assert err.max().item() < 1e-4, err
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("workload", ["v4", "v5"])
 def test_bench_workloads_one_gpu(workload):
-    rec = bench(["--workload", workload, "--batch", "16", "--no-b1"])
+    rec = bench(["--full", "--workload", workload, "--batch", "16", "--no-b1"])
     c = rec["config"]
     assert rec["scaling"] == "strong" and c["global_batch"] == 16 and c["workload"] == workload
     if workload == "v4":  # the native host-staged runtime: chunked per-rank DMA, link rate reported

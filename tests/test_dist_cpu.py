@@ -385,7 +385,7 @@ def _bench3(extra_env=None, extra_args=()):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"), "--gpus", "3",
            "--steps", "1", "--warmup", "0", "--batch-per-gpu", "4", "--root-batch", "2", "--device", "cpu",
-           "--no-ref-programs", *extra_args]
+           "--no-ref-programs", "--full", *extra_args]
     env = dict(os.environ, OMP_NUM_THREADS="1", **(extra_env or {}))
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -426,7 +426,8 @@ def test_bench_secondary_deadline_keeps_headline_gloo():
     port = free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "1", "--warmup", "0", "--batch-per-gpu", "2", "--device", "cpu", "--secondary-deadline-s", "15"]
+           "--steps", "1", "--warmup", "0", "--batch-per-gpu", "2", "--device", "cpu", "--full",
+           "--secondary-deadline-s", "15"]
     env = dict(os.environ, OMP_NUM_THREADS="1", ANX_BENCH_HANG_STAGE="reference_programs:1")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -450,7 +451,7 @@ def test_bench_reference_programs_gloo(world):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"), "--gpus", str(world),
            "--steps", "1", "--warmup", "0", "--batch-per-gpu", "2", "--device", "cpu", "--ref-steps", "1",
-           "--ref-batch-v4", "2", "--ref-batch-v5", str(world)]
+           "--ref-batch-v4", "2", "--ref-batch-v5", str(world), "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
