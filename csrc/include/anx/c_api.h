@@ -125,6 +125,11 @@ int anx_conv_pack(const int* plan, const float* w_kcff, float* packed, int* koff
    it may free buffers a previously captured HIP graph names: re-capture after it. */
 int anx_engine_set_knob(void* engine, const char* name, int value);
 int anx_engine_get_knob(void* engine, const char* name, int* value);
+/* Which kernels the engine's last tile_forward / stage1 / stage2 launched, recorded at the launch sites, as a
+   JSON object {"conv1": "fused_pool|fused|wino|mfma|direct", "pool1": "conv1_epilogue|input_transform|kernel",
+   "conv2": "f45|f35|mfma|direct", "pool2": "gemm_epilogue|kernel"} (null: not run yet) written into buf
+   (cap bytes; 128 suffice). No device call: safe between forwards and during stream capture. */
+int anx_engine_last_path(void* engine, char* buf, size_t cap);
 /* bf16 activation tap `i` of the last forward (FullEngine::tap) into dst; *elems = per-image count */
 int anx_full_tap(void* engine, int i, int N, void* dst, size_t* elems, void* stream);
 int anx_full_set_knob(void* engine, const char* name, int value);

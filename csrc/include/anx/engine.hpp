@@ -28,6 +28,17 @@ struct HostWeights {
   std::vector<float> w1, b1, w2, b2;  // KCFF weights, biases
 };
 
+// Which kernels the last tile_forward / stage1 / stage2 of an engine launched, written next to each launch
+// (never recomputed from the eligibility predicates: a second copy of them could drift from what runs).
+// Static strings; nullptr = that step has not run on this engine yet. With several launches per call
+// (chunks) the record holds the last one's.
+struct PathRecord {
+  const char* conv1 = nullptr;  // fused_pool | fused | wino | mfma | direct
+  const char* pool1 = nullptr;  // conv1_epilogue | input_transform | kernel
+  const char* conv2 = nullptr;  // f45 | f35 | mfma | direct
+  const char* pool2 = nullptr;  // gemm_epilogue | kernel
+};
+
 // Deterministic initialisers: constant mode reproduces the reference's golden
 // outputs (input 1.0, weights 0.01, bias 0); random mode is a seeded LCG (the reference's V1
 // uses rand() seeded by wall-clock, v1_serial/src/main.cpp:12 — not reproducible).
@@ -55,6 +66,8 @@ class BlocksEngine {
   // --graph) names freed buffers and must be re-captured. Throws (knobs restored) when a re-allocation fails.
   const Knobs& knobs() const { return k_; }
   int set_knob(const char* name, int value);  // 0, or -1 for a bad name / value (unchanged)
+  // Host state only (no device call): readable between forwards and during stream capture.
+  const PathRecord& last_path() const { return path_; }
 
   // x: [N, H, W, C0] device; y: [N, Hp2, Wp2, C2] device.
   hipError_t forward(const float* x, int N, float* y, hipStream_t s);
@@ -98,7 +111,9 @@ class BlocksEngine {
   int chunk_;  // images per internal launch chunk (32-bit index limits)
   Impl impl_;
   Knobs k_;
+  PathRecord path_;
   int wq_;     // padded conv2 input width
+  int full1_ = 0, full2_ = 0;  // conv1 / conv2 rows of the whole-image tile (use_winograd's "full image")
   // device buffers
   float *w1_ = nullptr, *b1d_ = nullptr, *w2_ = nullptr, *b2d_ = nullptr;  // KCFF (direct path)
   float *w1p_ = nullptr, *w2p_ = nullptr;                                  // packed (MFMA path)

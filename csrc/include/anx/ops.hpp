@@ -136,8 +136,9 @@ size_t conv1_wino_u_floats(int K);                   // transformed weights [25]
 void conv1_wino_weights_host(int K, int F, const float* w_kcff, std::vector<float>& u);
 // x: [N, Hin, W, 3] image rows; writes conv1 (+bias, optional ReLU) through `out`. Knobs: conv1_occ,
 // conv1_band, conv1_fused (1 / 2: the one-kernel form below instead of transform kernel + GEMM).
+// *one_kernel (if given) reports which of the two forms was launched.
 hipError_t conv1_wino(const Conv1WinoPlan& w, const float* x, float* V, const float* U, const float* bias, OutView out,
-                      bool relu, hipStream_t s, const Knobs& k);
+                      bool relu, hipStream_t s, const Knobs& k, bool* one_kernel = nullptr);
 // The one-kernel form (conv1_fused.hip): the input transform generated in LDS inside the GEMM, each
 // workgroup 32 tiles x all 96 filters (V never reaches HBM, U through an LDS-DMA ring). Eligible for
 // K == 96.

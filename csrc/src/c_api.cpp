@@ -497,9 +497,10 @@ int anx_rng_uniform(uint64_t seed, uint64_t stream, float* out, size_t n) {
 
 // ---------------------------------------------------------------------------------------- cost model
 namespace {
-int put_json(const std::string& j, char* buf, size_t cap) {
-  if (!buf || cap == 0) return fail("anx_cost: no output buffer");
-  if (j.size() + 1 > cap) return fail("anx_cost: output buffer too small (" + std::to_string(j.size() + 1) + " bytes)");
+int put_json(const std::string& j, char* buf, size_t cap, const char* who = "anx_cost") {
+  if (!buf || cap == 0) return fail(std::string(who) + ": no output buffer");
+  if (j.size() + 1 > cap)
+    return fail(std::string(who) + ": output buffer too small (" + std::to_string(j.size() + 1) + " bytes)");
   std::memcpy(buf, j.c_str(), j.size() + 1);
   return 0;
 }
@@ -543,5 +544,20 @@ extern "C" int anx_cost_dp_root_batch(int np, int batch, const char* overrides, 
   return guarded("anx_cost_dp_root_batch", [&] {
     *root_batch = anx::dp_root_batch(np, batch, anx::cost_params(overrides ? overrides : ""));
     return 0;
+  });
+}
+
+// The kernels the engine's last tile_forward / stage1 / stage2 launched (anx::PathRecord) as one JSON object;
+// a step that has not run yet is null. Host state only: no device call.
+extern "C" int anx_engine_last_path(void* e, char* buf, size_t cap) {
+  return guarded("anx_engine_last_path", [&] {
+    if (!e) return fail("anx_engine_last_path: no engine");
+    const anx::PathRecord& p = static_cast<anx::BlocksEngine*>(e)->last_path();
+    auto field = [](const char* name, const char* v) {
+      return std::string("\"") + name + "\": " + (v ? std::string("\"") + v + "\"" : std::string("null"));
+    };
+    return put_json("{" + field("conv1", p.conv1) + ", " + field("pool1", p.pool1) + ", " + field("conv2", p.conv2) +
+                        ", " + field("pool2", p.pool2) + "}",
+                    buf, cap, "anx_engine_last_path");
   });
 }

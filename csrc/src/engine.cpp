@@ -68,6 +68,13 @@ BlocksEngine::BlocksEngine(const BlockSpec& b1, const BlockSpec& b2, int H, int 
   if (b1.conv.P != 0) throw std::invalid_argument("conv1 padding must be 0 (row tiles read raw image rows)");
   if (d_.Hp2 <= 0 || d_.Wp2 <= 0) throw std::invalid_argument("input too small for AlexNet blocks 1-2");
   wq_ = d_.Wp1 + 2 * b2.conv.P;
+  {
+    // a full image's worth of conv rows for the Auto crossover: what the whole-image tile computes (H1 / H2, or
+    // one row less where the pool behind the conv drops the last row of an even map)
+    const TilePlan whole = make_plan(H, W, 1, Decomp::Overlap, b1, b2).tiles[0];
+    full1_ = whole.c1.size();
+    full2_ = whole.c2.size();
+  }
   const size_t per_img = std::max<size_t>(
       {static_cast<size_t>(H) * W * d_.C0, static_cast<size_t>(d_.H1) * d_.W1 * d_.C1,
        static_cast<size_t>(d_.Hp1 + 2 * b2.conv.P) * wq_ * d_.C1, static_cast<size_t>(d_.H2) * d_.W2 * d_.C2,
@@ -247,17 +254,22 @@ hipError_t BlocksEngine::conv1_chunk(const float* xc, int n, const TilePlan& t, 
   const ConvSpec& k1 = b1_.conv;
   const hip::OutView c1v{c1_ + static_cast<size_t>(c1_img0) * t.c1.size() * d_.W1 * d_.C1, t.c1.size(), d_.W1, d_.C1,
                          0, 0, 0};
-  if (impl_ == Impl::Mfma && wv1_ != nullptr && use_winograd(k_.conv1_algo, n, t.c1.size(), d_.H1)) {
+  if (impl_ == Impl::Mfma && wv1_ != nullptr && use_winograd(k_.conv1_algo, n, t.c1.size(), full1_)) {
     const hip::Conv1WinoPlan w = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
     if (hip::conv1_wino_v_floats(w) > wv1_cap_) return hipErrorInvalidValue;
-    return hip::conv1_wino(w, xc, wv1_, u1w_, b1d_, c1v, true, s, k_);
+    bool one_kernel = false;  // set by the launcher where it picks the one-kernel form
+    ANX_TRY(hip::conv1_wino(w, xc, wv1_, u1w_, b1d_, c1v, true, s, k_, &one_kernel));
+    path_.conv1 = one_kernel ? "fused" : "wino";
+    return hipSuccess;
   }
   if (impl_ == Impl::Mfma) {
     const hip::ConvPlan p =
         hip::make_conv_plan(n, t.in.size(), d_.W, d_.C0, k1.K, k1.F, k1.S, k1.groups, k_.force_vec4, k_.force_scalar);
     ANX_TRY(pack1(p));  // prepared by prepare() for the usual launches: a no-op then
+    path_.conv1 = "mfma";
     return hip::conv2d_mfma(p, xc, w1p_, koff1_, b1d_, c1v, true, s);
   }
+  path_.conv1 = "direct";
   return hip::conv2d_direct(xc, w1_, b1d_, c1_, n, t.in.size(), d_.W, d_.C0, k1.K, k1.F, k1.S, 0, k1.groups, true,
                             s);
 }
@@ -278,6 +290,7 @@ hipError_t BlocksEngine::stage1(const float* x, int N, const TilePlan& t, hipStr
     RoctxRange rx("anx pool1");
     ANX_TRY(hip::maxpool(c1_, n, t.c1.size(), d_.W1, d_.C1, b1_.pool.F, b1_.pool.S,
                          hip::OutView{q2_ + n0 * q_img, t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, b2_.conv.P, 0}, s));
+    path_.pool1 = "kernel";
   }
   return hipSuccess;
 }
@@ -287,25 +300,29 @@ hipError_t BlocksEngine::conv2_chunk(int n, const TilePlan& t, const float* qc, 
   RoctxRange rx("anx conv2+pool2+lrn");
   const ConvSpec& k2 = b2_.conv;
   const hip::OutView c2v{c2_, t.c2.size(), d_.W2, d_.C2, 0, 0, 0};
-  if (impl_ == Impl::Mfma && wv_ != nullptr && use_winograd(k_.conv2_algo, n, t.c2.size(), d_.H2)) {
+  if (impl_ == Impl::Mfma && wv_ != nullptr && use_winograd(k_.conv2_algo, n, t.c2.size(), full2_)) {
     const hip::WinoPlan w = hip::make_wino_plan(n, t.q.size(), wq_, d_.C1, k2.K, k2.groups, u2_m_);
     if (hip::wino_v_floats(w) > wv_cap_) return hipErrorInvalidValue;
     ANX_TRY(hip::wino_input(w, qc, wv_, s));
     ANX_TRY(hip::wino_conv2(w, wv_, u2w_, b2d_, c2v, true, s, k_));
+    path_.conv2 = w.m == 4 ? "f45" : "f35";  // wino_conv2 launches by the plan's tile
   } else if (impl_ == Impl::Mfma) {
     const hip::ConvPlan p =
         hip::make_conv_plan(n, t.q.size(), wq_, d_.C1, k2.K, k2.F, k2.S, k2.groups, k_.force_vec4, k_.force_scalar);
     ANX_TRY(pack2(p));
     ANX_TRY(hip::conv2d_mfma(p, qc, w2p_, koff2_, b2d_, c2v, true, s));
+    path_.conv2 = "mfma";
   } else {
     ANX_TRY(hip::conv2d_direct(qc, w2_, b2d_, c2_, n, t.q.size(), wq_, d_.C1, k2.K, k2.F, k2.S, 0, k2.groups, true,
                                s));
+    path_.conv2 = "direct";
   }
   return pool2_chunk(n, t, yc, s);
 }
 
 hipError_t BlocksEngine::pool2_chunk(int n, const TilePlan& t, float* yc, hipStream_t s) {
   const LrnSpec& l = b2_.lrn;
+  path_.pool2 = "kernel";  // every branch below pools the conv2 map with a kernel of its own
   if (b2_.has_lrn) {
     if (impl_ == Impl::Mfma)
       return hip::maxpool_lrn(c2_, yc, n, t.c2.size(), d_.W2, d_.C2, b2_.pool.F, b2_.pool.S, l.N, l.alpha, l.beta,
@@ -344,8 +361,8 @@ bool BlocksEngine::fused_pool1(int N, const TilePlan& t) const {
   const int chunk = std::min(chunk_, k_.chunk1 > 0 ? k_.chunk1 : chunk_);
   for (int n0 = 0; n0 < N; n0 += chunk) {
     const int n = std::min(chunk, N - n0), sub = k_.conv2_sub > 0 ? std::min(n, k_.conv2_sub) : n;
-    if (!use_winograd(k_.conv2_algo, sub, t.c2.size(), d_.H2) ||
-        !use_winograd(k_.conv2_algo, n - (n - 1) / sub * sub, t.c2.size(), d_.H2))
+    if (!use_winograd(k_.conv2_algo, sub, t.c2.size(), full2_) ||
+        !use_winograd(k_.conv2_algo, n - (n - 1) / sub * sub, t.c2.size(), full2_))
       return false;
   }
   return true;
@@ -353,24 +370,28 @@ bool BlocksEngine::fused_pool1(int N, const TilePlan& t) const {
 
 bool BlocksEngine::conv1_pools(int N, const TilePlan& t) const {
   if (!k_.conv1_pool || k_.conv1_fused == 0 || k_.conv1_sub > 0 || wv1_ == nullptr || !fused_pool1(N, t)) return false;
-  // whole images: every conv1 row, every pool1 row
-  if (t.c1.lo != 0 || t.c1.hi != d_.H1 || t.p1.lo != 0 || t.p1.hi != d_.Hp1) return false;
+  // whole images: every output row, from the first conv1 / pool1 row on. The whole-image tile holds the
+  // rows the output needs, not the map's last row where a pool drops it (an even H1 or Hp1): the kernels
+  // take the tile's own row counts (t.c1.size() conv1 rows, t.p1.size() pool1 rows)
+  if (t.out.lo != 0 || t.out.size() != d_.Hp2 || t.c1.lo != 0 || t.p1.lo != 0) return false;
   const int chunk = std::min(chunk_, k_.chunk1 > 0 ? k_.chunk1 : chunk_);
   const ConvSpec& k1 = b1_.conv;
   for (int n0 = 0; n0 < N; n0 += chunk) {
     const int n = std::min(chunk, N - n0);
-    if (!use_winograd(k_.conv1_algo, n, t.c1.size(), d_.H1)) return false;
+    if (!use_winograd(k_.conv1_algo, n, t.c1.size(), full1_)) return false;
     const hip::Conv1WinoPlan w = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
     const hip::OutView win{q2_, t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, b2_.conv.P, 0};
-    if (w.H1 != d_.H1 || !hip::conv1_fused_pool_eligible(w, win, d_.Hp1, d_.Wp1)) return false;
+    if (w.H1 != t.c1.size() || !hip::conv1_fused_pool_eligible(w, win, t.p1.size(), d_.Wp1)) return false;
   }
   return true;
 }
 
 bool BlocksEngine::conv2_pools(const TilePlan& t) const {
   const LrnSpec& l = b2_.lrn;
+  // whole images: every output row from conv2 row 0 (t.c2 ends at the last row pool2 reads, H2 or H2 - 1)
   return k_.conv2_pool && u2_m_ == 4 && b2_.has_lrn && l.N == 5 && d_.C2 == 256 && b2_.pool.F == 3 &&
-         b2_.pool.S == 2 && t.c2.lo == 0 && t.c2.size() == d_.H2 && t.out.lo == 0 && t.out.size() == d_.Hp2;
+         b2_.pool.S == 2 && t.c2.lo == 0 && t.c2.size() == t.q.size() - (b2_.conv.F - 1) && t.out.lo == 0 &&
+         t.out.size() == d_.Hp2;
 }
 
 hipError_t BlocksEngine::tile_forward(const float* x, int N, const TilePlan& t, float* y, hipStream_t s) {
@@ -404,8 +425,10 @@ hipError_t BlocksEngine::tile_forward(const float* x, int N, const TilePlan& t, 
       if (hip::wino_v_floats(w) > wv_cap_) return hipErrorInvalidValue;
       ANX_TRY(hip::wino_pool_input(w, c1_ + b0 * c1_img, t.c1.size(), d_.W1, t.q.lo, d_.Hp1, d_.Wp1, k2.P, t.c1.lo,
                                    wv_, s, b1_.pool.F, b1_.pool.S));
+      path_.pool1 = "input_transform";
       const hip::OutView c2v{c2_ + b0 * c2_img, t.c2.size(), d_.W2, d_.C2, 0, 0, 0};
       ANX_TRY(hip::wino_conv2(w, wv_, u2w_, b2d_, c2v, true, s, k_));
+      path_.conv2 = w.m == 4 ? "f45" : "f35";
     }
     ANX_TRY(pool2_chunk(n, t, y + n0 * y_img, s));
   }
@@ -421,7 +444,8 @@ hipError_t BlocksEngine::tile_forward_conv1_pool(const float* x, int N, const Ti
   const size_t in_img = static_cast<size_t>(t.in.size()) * d_.W * d_.C0;
   const size_t y_img = static_cast<size_t>(t.out.size()) * d_.Wp2 * d_.C2;
   const size_t q_img = q2_image_stride_floats(t);
-  const size_t p1_img = static_cast<size_t>(d_.Hp1) * d_.Wp1 * d_.C1;
+  const int hp1 = t.p1.size();  // pool1 rows of the tile: Hp1, or Hp1 - 1 where pool2 drops the last conv2 row
+  const size_t p1_img = static_cast<size_t>(hp1) * d_.Wp1 * d_.C1;
   const size_t c2_img = static_cast<size_t>(t.c2.size()) * d_.W2 * d_.C2;
   const int chunk = std::min(chunk_, k_.chunk1 > 0 ? k_.chunk1 : chunk_);
   for (int n0 = 0; n0 < N; n0 += chunk) {
@@ -430,7 +454,9 @@ hipError_t BlocksEngine::tile_forward_conv1_pool(const float* x, int N, const Ti
       RoctxRange rx("anx conv1+pool1");
       const hip::Conv1WinoPlan w1 = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
       const hip::OutView win{q2_ + n0 * q_img, t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, k2.P, 0};
-      ANX_TRY(hip::conv1_fused_pool(w1, x + n0 * in_img, u1w_, b1d_, win, c1_, d_.Hp1, d_.Wp1, true, s, k_.conv1_fused - 1));
+      ANX_TRY(hip::conv1_fused_pool(w1, x + n0 * in_img, u1w_, b1d_, win, c1_, hp1, d_.Wp1, true, s, k_.conv1_fused - 1));
+      path_.conv1 = "fused_pool";
+      path_.pool1 = "conv1_epilogue";
     }
     RoctxRange rx("anx conv2+pool2+lrn");
     const hip::Conv1WinoPlan w1 = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
@@ -446,22 +472,25 @@ hipError_t BlocksEngine::tile_forward_conv1_pool(const float* x, int N, const Ti
       const hip::WinoPlan w = hip::make_wino_plan(m, t.q.size(), wq_, d_.C1, k2.K, k2.groups, u2_m_);
       if (hip::wino_v_floats(w) > wv_cap_) return hipErrorInvalidValue;
       ANX_TRY(hip::wino_window_merge_input(w, q2_ + (n0 + b0) * q_img, c1_ + b0 * p1_img, b0, w1.ty, w1.tx, t.q.lo,
-                                           d_.Hp1, d_.Wp1, k2.P, wv_, s, u2_m_ == 4 ? k_.conv2_in_pg : 32));
+                                           hp1, d_.Wp1, k2.P, wv_, s, u2_m_ == 4 ? k_.conv2_in_pg : 32));
       if (pool2) {
         ty2 = w.ty;
         tx2 = w.tx;
         ANX_TRY(hip::wino_gemm_conv2_f45_pool(wv_, u2w_, b2d_, c2_ + b0 * pimg, p2 + b0 * pimg, w.P, w.ty, w.tx, w.Ho,
                                               w.Wo, d_.Hp2, d_.Wp2, w.K, true, s, k_.conv2_occ,
                                               k_.conv2_sched != 0));
+        path_.conv2 = "f45";
       } else {
         const hip::OutView c2v{c2_ + b0 * c2_img, t.c2.size(), d_.W2, d_.C2, 0, 0, 0};
         ANX_TRY(hip::wino_conv2(w, wv_, u2w_, b2d_, c2v, true, s, k_));
+        path_.conv2 = w.m == 4 ? "f45" : "f35";
       }
     }
     if (pool2) {
       const LrnSpec& l = b2_.lrn;
       ANX_TRY(hip::lrn_pooled_merge(c2_, p2, y + n0 * y_img, n, d_.Hp2, d_.Wp2, d_.C2, ty2, tx2, s2, l.N, l.alpha, l.beta,
                                     l.k, l.mode, s, k_.lrn_wgs));
+      path_.pool2 = "gemm_epilogue";
     } else {
       ANX_TRY(pool2_chunk(n, t, y + n0 * y_img, s));
     }

@@ -96,6 +96,7 @@ _SIGS = {
     "anx_engine_set_knob": (_I, [_P, C.c_char_p, _I]),
     "anx_engine_get_knob": (_I, [_P, C.c_char_p, C.POINTER(_I)]),
     "anx_default_knob": (_I, [C.c_char_p, C.POINTER(_I)]),
+    "anx_engine_last_path": (_I, [_P, C.c_char_p, _SZ]),
     "anx_conv2d_mfma": (_I, [C.POINTER(_I), _P, _P, _P, _P, _P] + [_I] * 6 + [_I, _P]),
     "anx_cpu_conv2d": (_I, [_P, _P, _P, _P] + [_I] * 10),
     "anx_cpu_maxpool": (_I, [_P, _P] + [_I] * 6),

@@ -132,6 +132,21 @@ class AlexNetBlocks:
             raise ValueError("kernel knobs belong to the GPU engine")
         return read_knob(self._engine, name)
 
+    def last_path(self, lane: int = 0) -> dict:
+        """Which kernels the last forward / tile_forward / stage1 / stage2 of this model's GPU engine launched
+        (``lane`` > 0: that side lane's engine): ``{"conv1": "fused_pool" | "fused" | "wino" | "mfma" | "direct",
+        "pool1": "conv1_epilogue" | "input_transform" | "kernel", "conv2": "f45" | "f35" | "mfma" | "direct",
+        "pool2": "gemm_epilogue" | "kernel"}``, ``None`` for a step that has not run. The engine records it where
+        it launches (not from the eligibility rules), and reading it makes no device call."""
+        if not self.is_cuda:
+            raise ValueError("last_path belongs to the GPU engine")
+        if lane:
+            return self._lanes[lane - 1].last_path()
+        import json
+        buf = C.create_string_buffer(256)
+        nat.call("anx_engine_last_path", self._engine, buf, len(buf))
+        return json.loads(buf.value.decode())
+
     # ------------------------------------------------------------------ engine lifetime
     def _ensure(self, n: int) -> None:
         if self._engine is not None and (n <= self._cap or not self.is_cuda):

@@ -503,6 +503,9 @@ def test_conv1_pool_epilogue_bitwise(cuda, N, kn):
     off = AlexNetBlocks(device=cuda, init="rand", seed=21, max_batch=N, knobs={**base, "conv1_pool": 0})
     y = on(x)
     assert torch.equal(y, off(x))
+    pon, poff = on.last_path(), off.last_path()  # neither arm may fall back silently
+    assert (pon["conv1"], pon["pool1"]) == ("fused_pool", "conv1_epilogue")
+    assert (poff["conv1"], poff["pool1"]) == ("fused", "input_transform")
     y.fill_(float("nan"))  # every pooled pixel rewritten each call (the window border stays zero)
     on(x, out=y)
     assert torch.equal(y, off(x))
@@ -514,13 +517,16 @@ def test_conv1_pool_epilogue_bitwise(cuda, N, kn):
                                           (64, {}, None, "div_n"), (130, {}, None, "div_n"),
                                           (40, {"chunk1": 16}, None, "div_n"), (64, {"conv2_sub": 24}, None, "div_n"),
                                           (20, {"chunk1": 9, "conv2_sub": 4}, None, "raw"),
-                                          (5, {}, (195, 259), "div_n")])
+                                          (5, {}, (195, 259), "div_n"), (9, {}, (195, 211), "div_n")])
 def test_conv2_pool_epilogue_bitwise(cuda, N, kn, hw, mode):
     """pool2 in the F(4x4,5x5) Conv2 GEMM's epilogue (tuning knob conv2_pool: the conv2 map never reaches HBM;
     windows straddling two workgroups' 32-tile ranges merged from a side buffer by the LRN kernel) gives
     the same bits as the GEMM writing its map and maxpool_lrn pooling it: partial workgroups, chunks,
     Conv2 sub-chunks (the merge's image index inside a GEMM launch), both LRN modes and a non-square
-    image; the whole output against the fp64 oracle too."""
+    image (195x211: 23x25 conv2 maps, 6x7 tiles); the whole output against the fp64 oracle too. The path that
+    ran is asserted (last_path). 195x259 is past the fused chain's window limit (a 35-column padded Conv2
+    window): there both engines must run pool1 and pool2 as kernels of their own, whatever the knob says, and
+    still agree with each other and the oracle."""
     H, W = hw if hw else (227, 227)
     x = init_input(N, "rand", seed=23, H=H, W=W).to(cuda)
     base = {**WINO1, **WINO2, **kn}
@@ -530,6 +536,12 @@ def test_conv2_pool_epilogue_bitwise(cuda, N, kn, hw, mode):
     assert on.get_knob("conv2_pool") == 1 and off.get_knob("conv2_pool") == 0
     y = on(x)
     assert torch.equal(y, off(x))
+    if hw == (195, 259):
+        unfused = {"conv1": "fused", "pool1": "kernel", "conv2": "f45", "pool2": "kernel"}
+        assert on.last_path() == unfused and off.last_path() == unfused
+    else:
+        assert on.last_path()["pool2"] == "gemm_epilogue" and on.last_path()["conv2"] == "f45"
+        assert off.last_path()["pool2"] == "kernel" and off.last_path()["conv2"] == "f45"
     y.fill_(float("nan"))  # every pooled pixel rewritten each call
     on(x, out=y)
     assert torch.equal(y, off(x))
@@ -550,7 +562,30 @@ def test_conv2_hand_schedule_bitwise(cuda, N, kn):
     assert hand.get_knob("conv2_sched") == 1 and comp.get_knob("conv2_sched") == 0
     y = hand(x)
     assert torch.equal(y, comp(x))
+    for m in (hand, comp):  # the F(4x4,5x5) GEMM (here with pool2 in its epilogue), not a fallback
+        assert (m.last_path()["conv2"], m.last_path()["pool2"]) == ("f45", "gemm_epilogue")
     ref = blocks_forward_all(x, hand.weights, hand.b1, hand.b2, device=cuda)
+    torch.testing.assert_close(y.double(), ref.to(cuda), rtol=2e-5, atol=2e-6)
+
+
+@pytest.mark.parametrize("N,kn,hw", [(9, {}, None), (64, {}, None), (130, {}, None), (64, {"conv2_sub": 24}, None),
+                                     (9, {}, (131, 179))])
+def test_conv2_in_pg16_bitwise(cuda, N, kn, hw):
+    """The merged Conv2 input transform on 16 channels per workgroup (tuning knob conv2_in_pg = 16:
+    pool_wino_in_kernel<4, 16, 256, false, true>, 256 threads, half the LDS band) gives the same V, hence the same
+    output bits, as the 32-channel form: partial Conv1 workgroups, a sub-chunked launch (its offset into the
+    Conv1 launch's tile numbering) and a 15x21 map; both on the fully fused chain."""
+    H, W = hw if hw else (227, 227)
+    x = init_input(N, "rand", seed=41, H=H, W=W).to(cuda)
+    mk = lambda pg: AlexNetBlocks(device=cuda, init="rand", seed=41, max_batch=N, H=H, W=W,
+                                  knobs={**WINO1, **WINO2, **kn, "conv2_in_pg": pg})
+    pg16, pg32 = mk(16), mk(32)
+    assert pg16.get_knob("conv2_in_pg") == 16 and pg32.get_knob("conv2_in_pg") == 32
+    y = pg16(x)
+    assert torch.equal(y, pg32(x))
+    fused = {"conv1": "fused_pool", "pool1": "conv1_epilogue", "conv2": "f45", "pool2": "gemm_epilogue"}
+    assert pg16.last_path() == fused and pg32.last_path() == fused
+    ref = blocks_forward_all(x, pg16.weights, pg16.b1, pg16.b2, device=cuda)
     torch.testing.assert_close(y.double(), ref.to(cuda), rtol=2e-5, atol=2e-6)
 
 

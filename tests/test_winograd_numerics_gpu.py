@@ -50,6 +50,52 @@ def test_conv2_winograd_randn_he(cuda, N, groups, tile):
     assert _rel_to_terms(y, x, w.to(cuda), b, 1, 0, groups) < BOUND_CONV2
 
 
+WINDOWS = [(7, 7), (8, 9), (12, 13), (13, 14), (14, 31), (31, 20)]  # (Hq, Wq): outputs (Hq - 4) x (Wq - 4)
+WINDOW_CASES = [(hq, wq, n, g, t) for hq, wq in WINDOWS for n in ((9, 40) if hq <= 8 else (9,))
+                for g, t in ((1, 3), (2, 3), (1, 4))]
+
+
+@pytest.mark.parametrize("Hq,Wq,N,groups,tile", WINDOW_CASES)
+def test_conv2_winograd_randn_he_windows(cuda, Hq, Wq, N, groups, tile):
+    """test_conv2_winograd_randn_he at other Conv2 windows (it only ever runs 31x31, i.e. a last tile with 3
+    valid rows and columns on F(4x4,5x5) and none partial on F(3x3,5x5)): outputs 3x3 (one tile), 4x5, 8x9
+    (4x4 remainders 0 / 1), 9x10 (1 / 2), 10x27 and 27x16 (2 / 3, 3 / 0), non-square; 9 images, and 40 for the two
+    smallest (several images per 32- or 64-tile workgroup). Same zero border, error measure and bound: the
+    transforms are the 31x31 ones. Every output pixel must be written (the map starts as NaN).
+    MI355X run, max error / sum|x*w| per window (F(3,5) groups 1, groups 2, F(4,5)), means 0.8-1.7e-7:
+    7x7 2.3e-6 2.5e-6 2.7e-6 (40 images 2.4e-6 3.0e-6 2.9e-6); 8x9 1.0e-6 1.1e-6 2.4e-6 (40 images 1.2e-6 1.1e-6
+    3.6e-6); 12x13 1.5e-6 1.3e-6 5.0e-6; 13x14 1.8e-6 1.6e-6 2.1e-6; 14x31 2.0e-6 2.2e-6 2.5e-6; 31x20 1.5e-6
+    2.2e-6 2.9e-6. The largest, 5.0e-6, is half the bound."""
+    torch.manual_seed(21 + N + 100 * Hq + Wq)
+    C, K = 96, 256
+    x = torch.randn(N, Hq, Wq, C, device=cuda)
+    x[:, :2] = 0
+    x[:, -2:] = 0
+    x[:, :, :2] = 0
+    x[:, :, -2:] = 0  # the zero border of the conv2 window
+    w = torch.randn(K, C // groups, 5, 5) * math.sqrt(2.0 / (C // groups * 25))
+    b = torch.randn(K, device=cuda) * 0.1
+    y = torch.full((N, Hq - 4, Wq - 4, K), float("nan"), device=cuda)
+    nat.call("anx_conv2_wino_tile", x.data_ptr(), N, Hq, Wq, C, w.contiguous().data_ptr(), K, groups, b.data_ptr(),
+             y.data_ptr(), 0, nat.stream_ptr(cuda), tile)
+    assert torch.isfinite(y).all()
+    assert _rel_to_terms(y, x, w.to(cuda), b, 1, 0, groups) < BOUND_CONV2
+
+
+@pytest.mark.parametrize("C,K,groups,tile", [(64, 256, 1, 3), (96, 200, 1, 4), (96, 256, 2, 4), (96, 256, 1, 5)])
+def test_conv2_winograd_refuses_other_shapes(cuda, C, K, groups, tile):
+    """A shape the Winograd entry has no kernel for is an error, and the output is left untouched."""
+    x = torch.zeros(2, 12, 13, C, device=cuda)
+    w = torch.zeros(K, C // groups, 5, 5)
+    b = torch.zeros(K, device=cuda)
+    y = torch.full((2, 8, 9, K), float("nan"), device=cuda)
+    with pytest.raises(nat.NativeError):
+        nat.call("anx_conv2_wino_tile", x.data_ptr(), 2, 12, 13, C, w.contiguous().data_ptr(), K, groups, b.data_ptr(),
+                 y.data_ptr(), 0, nat.stream_ptr(cuda), tile)
+    torch.cuda.synchronize()
+    assert torch.isnan(y).all()
+
+
 @pytest.mark.parametrize("N", [5, 70])
 def test_conv1_polyphase_winograd_randn_he(cuda, N):
     """Conv1 (227x227x3, 11x11/4, 96 filters) on the polyphase Winograd path: randn inputs."""
