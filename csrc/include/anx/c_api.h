@@ -69,6 +69,22 @@ int anx_engine_forward(void* e, const float* x, int N, float* y, void* stream);
 int anx_engine_tile_forward(void* e, const float* x, int N, const anx_tile_c* t, float* y, void* stream);
 int anx_engine_stage1(void* e, const float* x, int N, const anx_tile_c* t, void* stream);
 int anx_engine_stage2(void* e, int N, const anx_tile_c* t, float* y, void* stream);
+/* Byte input ([N, rows, W, C0] uint8): a byte b of channel c means fmaf((float)b, scale[c], offset[c]), one
+   fused multiply-add in fp32 (default scale 1/255, offset 0; set_input_norm takes C0 values each). The _u8
+   entry points have the contracts of their float twins and give the output of the float twin fed the decoded
+   image, bit for bit. Knob conv1_u8 = 1: where the one-kernel Conv1 runs it reads the bytes itself; everywhere
+   else (and with the default conv1_u8 = 0) the launch chunk is decoded into a workspace that the first such call allocates (never inside a stream
+   capture: warm up once before capturing). anx_engine_last_input writes "f32", "u8_fused" or "u8_decode"
+   (how the last tile_forward / stage1 fed Conv1; "" before the first) into buf; no device call. */
+int anx_engine_set_input_norm(void* e, const float* scale, const float* offset);
+int anx_engine_forward_u8(void* e, const uint8_t* x, int N, float* y, void* stream);
+int anx_engine_tile_forward_u8(void* e, const uint8_t* x, int N, const anx_tile_c* t, float* y, void* stream);
+int anx_engine_stage1_u8(void* e, const uint8_t* x, int N, const anx_tile_c* t, void* stream);
+int anx_engine_last_input(void* e, char* buf, size_t cap);
+/* the decode alone: y[i] = fmaf((float)x[i], scale[i % C], offset[i % C]), n elements from any byte address
+   (device, 1 <= C <= 16; host, any C) */
+int anx_decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, const float* offset, void* stream);
+int anx_cpu_decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, const float* offset);
 /* conv2 input window geometry: pointer of (image n, pool1 row r), row stride and image stride (floats). */
 int anx_engine_window(void* e, const anx_tile_c* t, int n, int r, float** ptr, size_t* row_floats,
                       size_t* image_floats);
@@ -92,6 +108,11 @@ int anx_cpu_engine_destroy(void* e);
 int anx_cpu_engine_tile_forward(void* e, const float* x, int N, const anx_tile_c* t, float* y);
 int anx_cpu_engine_stage1(void* e, const float* x, int N, const anx_tile_c* t);
 int anx_cpu_engine_stage2(void* e, int N, const anx_tile_c* t, float* y);
+/* byte input on the host engine: decoded with the same fmaf, then the float code */
+int anx_cpu_engine_set_input_norm(void* e, const float* scale, const float* offset);
+int anx_cpu_engine_forward_u8(void* e, const uint8_t* x, int N, float* y);
+int anx_cpu_engine_tile_forward_u8(void* e, const uint8_t* x, int N, const anx_tile_c* t, float* y);
+int anx_cpu_engine_stage1_u8(void* e, const uint8_t* x, int N, const anx_tile_c* t);
 int anx_cpu_engine_window(void* e, const anx_tile_c* t, int n, int r, float** ptr, size_t* row_floats,
                           size_t* image_floats);
 /* strided host copy (memcpy per row) */

@@ -19,6 +19,12 @@ class CpuBlocks {
   // stage1 fills pool1 rows t.p1 of the conv2 input window (zero elsewhere); stage2 consumes it.
   void stage1(const float* x, int N, const TilePlan& t);
   void stage2(int N, const TilePlan& t, float* y);
+  // Byte input (same meaning and contracts as BlocksEngine's): decoded on the host with cpu::decode_u8, then
+  // the float code. scale / offset hold C0 values each; default 1/255 and 0.
+  void set_input_norm(const float* scale, const float* offset);
+  void forward_u8(const uint8_t* x, int N, float* y);
+  void tile_forward_u8(const uint8_t* x, int N, const TilePlan& t, float* y);
+  void stage1_u8(const uint8_t* x, int N, const TilePlan& t);
   float* window_row(const TilePlan& t, int n, int r);
   size_t window_row_floats() const { return static_cast<size_t>(wq_) * d_.C1; }
 
@@ -28,6 +34,7 @@ class CpuBlocks {
   HostWeights w_;
   int wq_;
   std::vector<float> c1_, p1_, q_, c2_, p2_;
+  std::vector<float> sc_, of_, xdec_;  // byte input: scale / offset per channel, the decoded tile
 };
 
 }  // namespace anx

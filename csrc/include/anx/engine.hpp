@@ -68,6 +68,24 @@ class BlocksEngine {
   int set_knob(const char* name, int value);  // 0, or -1 for a bad name / value (unchanged)
   // Host state only (no device call): readable between forwards and during stream capture.
   const PathRecord& last_path() const { return path_; }
+  // How the last tile_forward / stage1 (either input type) fed Conv1, written next to the launch like
+  // PathRecord: "f32" (float input), "u8_fused" (the one-kernel Conv1 loaded the bytes itself), "u8_decode"
+  // (decode kernel into the workspace, then the float path); nullptr before the first call. Host state only.
+  const char* last_input() const { return input_; }
+
+  // Byte input. A byte b of channel c means fmaf(float(b), scale[c], offset[c]) (cpu::decode_u8); scale and
+  // offset hold C0 values each. Default: scale 1/255, offset 0. Throws for C0 > hip::kU8MaxC.
+  void set_input_norm(const float* scale, const float* offset);
+  // The twins of forward / tile_forward / stage1 below for x as bytes ([N, rows, W, C0] uint8): same
+  // contracts, same output as the float entry point fed the decoded image, bit for bit. Where the float path
+  // launches the one-kernel Conv1 (conv1_fused / conv1_fused_pool) and Knobs::conv1_u8 is set, that kernel
+  // reads the bytes and no float copy of the input exists; everywhere else (and by default: conv1_u8 = 0
+  // measured faster) the launch chunk is decoded into a workspace first. That workspace (one launch chunk of floats) is allocated by the first byte call that
+  // needs it, never inside a stream capture (such a call fails with hipErrorStreamCaptureUnsupported): like
+  // set_knob, warm up once before capturing.
+  hipError_t forward_u8(const uint8_t* x, int N, float* y, hipStream_t s);
+  hipError_t tile_forward_u8(const uint8_t* x, int N, const TilePlan& t, float* y, hipStream_t s);
+  hipError_t stage1_u8(const uint8_t* x, int N, const TilePlan& t, hipStream_t s, int n_lo = 0, int n_hi = -1);
 
   // x: [N, H, W, C0] device; y: [N, Hp2, Wp2, C2] device.
   hipError_t forward(const float* x, int N, float* y, hipStream_t s);
@@ -94,8 +112,18 @@ class BlocksEngine {
   hipError_t pack1(const hip::ConvPlan& p);  // direct-path packed weights for plan p (no-op when current)
   hipError_t pack2(const hip::ConvPlan& p);
   hipError_t ensure_window(const TilePlan& t, int N, hipStream_t s);
+  // An input image batch: floats, or bytes (u8 != nullptr)
+  struct In {
+    const float* f32;
+    const uint8_t* u8;
+    In at(size_t elems) const { return u8 ? In{nullptr, u8 + elems} : In{f32 + elems, nullptr}; }
+  };
+  hipError_t tile_forward_in(In x, int N, const TilePlan& t, float* y, hipStream_t s);
+  hipError_t stage1_in(In x, int N, const TilePlan& t, hipStream_t s, int n_lo, int n_hi);
+  // bytes of a launch chunk -> xdec_ (allocated on first use, outside stream capture)
+  hipError_t decode_chunk(const uint8_t* x, size_t elems, hipStream_t s);
   // conv1 (+ReLU) of n images into c1_ starting at image c1_img0
-  hipError_t conv1_chunk(const float* xc, int n, const TilePlan& t, hipStream_t s, int c1_img0 = 0);
+  hipError_t conv1_chunk(In xc, int n, const TilePlan& t, hipStream_t s, int c1_img0 = 0);
   hipError_t conv2_chunk(int n, const TilePlan& t, const float* qc, float* yc, hipStream_t s);
   hipError_t pool2_chunk(int n, const TilePlan& t, float* yc, hipStream_t s);  // c2_ -> y (+LRN)
   // Whether tile_forward of N images runs pool1 inside the Winograd input transform (Knobs::fuse_pool1)
@@ -103,7 +131,7 @@ class BlocksEngine {
   // ... and whether pool1 runs inside the one-kernel Conv1 instead (Knobs::conv1_pool; whole images only)
   bool conv1_pools(int N, const TilePlan& t) const;
   bool conv2_pools(const TilePlan& t) const;  // pool2 in the F(4x4,5x5) GEMM's epilogue (Knobs::conv2_pool)
-  hipError_t tile_forward_conv1_pool(const float* x, int N, const TilePlan& t, float* y, hipStream_t s);
+  hipError_t tile_forward_conv1_pool(In x, int N, const TilePlan& t, float* y, hipStream_t s);
 
   BlockSpec b1_, b2_;
   BlocksDims d_;
@@ -112,6 +140,10 @@ class BlocksEngine {
   Impl impl_;
   Knobs k_;
   PathRecord path_;
+  const char* input_ = nullptr;  // last_input()
+  hip::U8Norm norm_{};           // byte input: scale / offset per channel (C == 0: C0 too large for byte input)
+  float* xdec_ = nullptr;        // decoded launch chunk (byte input on the float paths)
+  size_t xdec_cap_ = 0;
   int wq_;     // padded conv2 input width
   int full1_ = 0, full2_ = 0;  // conv1 / conv2 rows of the whole-image tile (use_winograd's "full image")
   // device buffers

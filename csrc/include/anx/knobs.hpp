@@ -64,6 +64,13 @@ struct Knobs {
                            // the 55x55 map stays in LDS, pooled pixels go to the conv2 window, straddling windows'
                            // partial maxima to a side buffer merged by the Conv2 input transform), 0 = Conv1 writes its
                            // map and the input transform pools it
+  int conv1_u8 = 0;        // byte input (forward_u8 / tile_forward_u8 / stage1_u8) where the one-kernel Conv1 runs: 1 = that
+                           // kernel loads the bytes itself and decodes them in registers (no float copy of the
+                           // input on the device), 0 (default, by measurement) = the decode kernel into a workspace,
+                           // then the float kernel. Same bits either way; every other Conv1 path always decodes
+                           // first. 128 images on two lanes: float input 0.356 ms, 0 = 0.372 ms, 1 = 0.441 ms per
+                           // step (the byte kernel alone: 96.8 us vs 83.1 + 17.2 us per 64 images, but it slows
+                           // the other lane's kernels; profiles/u8_input/)
   int conv1_sub = 0;       // fused tile_forward: images per Conv1 (input transform + GEMM) launch pair inside a
                            // chunk (0 = the whole chunk); the V workspace is rewritten in place per sub-chunk, so
                            // a small one is written and re-read inside the 256 MB Infinity Cache
@@ -90,7 +97,7 @@ struct Knobs {
 
 // Built-in defaults, overridden by ANX_CONV1_ALGO, ANX_CONV2_ALGO, ANX_CHUNK1, ANX_CHUNK2,
 // ANX_BF16_GLDS, ANX_BF16_BIG, ANX_CONV1_OCC, ANX_CONV2_OCC, ANX_CONV1_BAND, ANX_FUSE_POOL1,
-// ANX_CONV1_SUB, ANX_CONV2_SUB, ANX_CONV1_FUSED, ANX_CONV1_POOL, ANX_CONV2_POOL, ANX_CONV2_TILE,
+// ANX_CONV1_SUB, ANX_CONV2_SUB, ANX_CONV1_U8, ANX_CONV1_FUSED, ANX_CONV1_POOL, ANX_CONV2_POOL, ANX_CONV2_TILE,
 // ANX_CONV2_SCHED, ANX_LRN_WGS when set.
 Knobs default_knobs();
 

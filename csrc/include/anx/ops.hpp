@@ -29,6 +29,10 @@ void relu(float* x, size_t n);
 void maxpool(const float* x, float* y, int N, int H, int W, int C, int F, int S);
 void lrn(const float* x, float* y, int N, int H, int W, int C, int size, float alpha, float beta, float k,
          LrnMode mode);
+// Byte image -> float: y[i] = fmaf(float(x[i]), scale[i % C], offset[i % C]), one fused multiply-add in fp32.
+// THE definition of the byte input's meaning: hip::decode_u8 and the byte loader of the one-kernel Conv1
+// evaluate the same expression, so every path is comparable bit for bit. The reference has no byte input.
+void decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, const float* offset);
 }  // namespace cpu
 
 // ----------------------------------------------------------------------------------------
@@ -160,6 +164,26 @@ __host__ __device__ inline bool pool1_straddles(int n, int py, int px, int ty1, 
 bool conv1_fused_pool_eligible(const Conv1WinoPlan& w, const OutView& window, int Hp, int Wp);
 hipError_t conv1_fused_pool(const Conv1WinoPlan& w, const float* x, const float* U, const float* bias, OutView window,
                             float* p1, int Hp, int Wp, bool relu, hipStream_t s, int um = 0);
+// Whether conv1_wino launches the one-kernel form for this plan, destination and knobs (the one definition:
+// the engine asks it before it decides how a byte image reaches Conv1).
+bool conv1_wino_one_kernel(const Conv1WinoPlan& w, const OutView& out, const Knobs& k);
+
+// Byte images (uint8 NHWC). A byte b of channel c means fmaf(float(b), sc[c], of[c]) (cpu::decode_u8).
+constexpr int kU8MaxC = 16;
+struct U8Norm {
+  int C;
+  float sc[kU8MaxC], of[kU8MaxC];
+};
+// y[i] = fmaf(float(x[i]), sc[i % C], of[i % C]) for n elements; x may start at any byte address and n may be
+// anything (16-B loads where the source is aligned, single bytes before and after).
+hipError_t decode_u8(const uint8_t* x, float* y, size_t n, const U8Norm& nm, hipStream_t s);
+// The one-kernel Conv1 forms reading the byte image directly (C == 3): the decode happens in the X' loader,
+// no fp32 copy of the input exists. Same eligibility, output and bits as decode_u8 + the fp32 forms.
+hipError_t conv1_fused_u8(const Conv1WinoPlan& w, const uint8_t* x, const U8Norm& nm, const float* U, const float* bias,
+                          OutView out, bool relu, hipStream_t s);
+hipError_t conv1_fused_pool_u8(const Conv1WinoPlan& w, const uint8_t* x, const U8Norm& nm, const float* U,
+                               const float* bias, OutView window, float* p1, int Hp, int Wp, bool relu, hipStream_t s,
+                               int um = 0);
 
 // The fused Winograd GEMM + output transform (wino_gemm.hip). V [P][points][C], U [points][K][C/groups]
 // (row = filter), bias + optional ReLU, NHWC store through `out` (Cb, c_off multiples of 4). P tiles of

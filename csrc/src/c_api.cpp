@@ -118,7 +118,7 @@ anx::hip::ConvPlan plan_from_ints(const int* o) {
 extern "C" {
 
 const char* anx_last_error(void) { return g_err.c_str(); }
-int anx_abi_version(void) { return 1; }
+int anx_abi_version(void) { return 2; }  // 2: byte input (anx_*_u8, anx_*_set_input_norm, anx_engine_last_input)
 
 int anx_device_count(void) {
   int n = 0;
@@ -226,6 +226,92 @@ int anx_engine_stage1(void* e, const float* x, int N, const anx_tile_c* t, void*
 int anx_engine_stage2(void* e, int N, const anx_tile_c* t, float* y, void* stream) {
   return guarded("anx_engine_stage2", [&] {
     return hip_status(static_cast<anx::BlocksEngine*>(e)->stage2(N, tile_from_c(*t), y, S(stream)), "engine stage2");
+  });
+}
+
+int anx_engine_set_input_norm(void* e, const float* scale, const float* offset) {
+  return guarded("anx_engine_set_input_norm", [&] {
+    if (!e || !scale || !offset) return fail("anx_engine_set_input_norm: null argument");
+    static_cast<anx::BlocksEngine*>(e)->set_input_norm(scale, offset);
+    return 0;
+  });
+}
+
+int anx_engine_forward_u8(void* e, const uint8_t* x, int N, float* y, void* stream) {
+  return guarded("anx_engine_forward_u8", [&] {
+    return hip_status(static_cast<anx::BlocksEngine*>(e)->forward_u8(x, N, y, S(stream)), "engine forward_u8");
+  });
+}
+
+int anx_engine_tile_forward_u8(void* e, const uint8_t* x, int N, const anx_tile_c* t, float* y, void* stream) {
+  return guarded("anx_engine_tile_forward_u8", [&] {
+    return hip_status(static_cast<anx::BlocksEngine*>(e)->tile_forward_u8(x, N, tile_from_c(*t), y, S(stream)),
+                      "engine tile_forward_u8");
+  });
+}
+
+int anx_engine_stage1_u8(void* e, const uint8_t* x, int N, const anx_tile_c* t, void* stream) {
+  return guarded("anx_engine_stage1_u8", [&] {
+    return hip_status(static_cast<anx::BlocksEngine*>(e)->stage1_u8(x, N, tile_from_c(*t), S(stream)),
+                      "engine stage1_u8");
+  });
+}
+
+int anx_engine_last_input(void* e, char* buf, size_t cap) {
+  return guarded("anx_engine_last_input", [&] {
+    if (!e || !buf || cap == 0) return fail("anx_engine_last_input: no engine or buffer");
+    const char* v = static_cast<anx::BlocksEngine*>(e)->last_input();
+    const std::string sv = v ? v : "";
+    if (sv.size() + 1 > cap) return fail("anx_engine_last_input: output buffer too small");
+    std::memcpy(buf, sv.c_str(), sv.size() + 1);
+    return 0;
+  });
+}
+
+int anx_decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, const float* offset, void* stream) {
+  return guarded("anx_decode_u8", [&] {
+    if (C < 1 || C > anx::hip::kU8MaxC || !scale || !offset) return fail("anx_decode_u8: 1 <= C <= 16 scale / offset values");
+    anx::hip::U8Norm nm{};
+    nm.C = C;
+    for (int c = 0; c < C; ++c) nm.sc[c] = scale[c], nm.of[c] = offset[c];
+    return hip_status(anx::hip::decode_u8(x, y, n, nm, S(stream)), "decode_u8");
+  });
+}
+
+int anx_cpu_decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, const float* offset) {
+  return guarded("anx_cpu_decode_u8", [&] {
+    if (C < 1 || !scale || !offset) return fail("anx_cpu_decode_u8: C >= 1 scale / offset values");
+    anx::cpu::decode_u8(x, y, n, C, scale, offset);
+    return 0;
+  });
+}
+
+int anx_cpu_engine_set_input_norm(void* e, const float* scale, const float* offset) {
+  return guarded("anx_cpu_engine_set_input_norm", [&] {
+    if (!e || !scale || !offset) return fail("anx_cpu_engine_set_input_norm: null argument");
+    static_cast<anx::CpuBlocks*>(e)->set_input_norm(scale, offset);
+    return 0;
+  });
+}
+
+int anx_cpu_engine_forward_u8(void* e, const uint8_t* x, int N, float* y) {
+  return guarded("anx_cpu_engine_forward_u8", [&] {
+    static_cast<anx::CpuBlocks*>(e)->forward_u8(x, N, y);
+    return 0;
+  });
+}
+
+int anx_cpu_engine_tile_forward_u8(void* e, const uint8_t* x, int N, const anx_tile_c* t, float* y) {
+  return guarded("anx_cpu_engine_tile_forward_u8", [&] {
+    static_cast<anx::CpuBlocks*>(e)->tile_forward_u8(x, N, tile_from_c(*t), y);
+    return 0;
+  });
+}
+
+int anx_cpu_engine_stage1_u8(void* e, const uint8_t* x, int N, const anx_tile_c* t) {
+  return guarded("anx_cpu_engine_stage1_u8", [&] {
+    static_cast<anx::CpuBlocks*>(e)->stage1_u8(x, N, tile_from_c(*t));
+    return 0;
   });
 }
 

@@ -7,7 +7,29 @@
 namespace anx {
 
 CpuBlocks::CpuBlocks(const BlockSpec& b1, const BlockSpec& b2, int H, int W, const HostWeights& w)
-    : b1_(b1), b2_(b2), d_(blocks_dims(H, W, b1, b2)), w_(w), wq_(d_.Wp1 + 2 * b2.conv.P) {}
+    : b1_(b1), b2_(b2), d_(blocks_dims(H, W, b1, b2)), w_(w), wq_(d_.Wp1 + 2 * b2.conv.P),
+      sc_(d_.C0, 1.0f / 255.0f), of_(d_.C0, 0.f) {}
+
+void CpuBlocks::set_input_norm(const float* scale, const float* offset) {
+  sc_.assign(scale, scale + d_.C0);
+  of_.assign(offset, offset + d_.C0);
+}
+
+void CpuBlocks::stage1_u8(const uint8_t* x, int N, const TilePlan& t) {
+  xdec_.resize(static_cast<size_t>(N) * t.in.size() * d_.W * d_.C0);
+  cpu::decode_u8(x, xdec_.data(), xdec_.size(), d_.C0, sc_.data(), of_.data());
+  stage1(xdec_.data(), N, t);
+}
+
+void CpuBlocks::tile_forward_u8(const uint8_t* x, int N, const TilePlan& t, float* y) {
+  stage1_u8(x, N, t);
+  stage2(N, t, y);
+}
+
+void CpuBlocks::forward_u8(const uint8_t* x, int N, float* y) {
+  const DecompPlan p = make_plan(d_.H, d_.W, 1, Decomp::Overlap, b1_, b2_);
+  tile_forward_u8(x, N, p.tiles[0], y);
+}
 
 float* CpuBlocks::window_row(const TilePlan& t, int n, int r) {
   return q_.data() + (static_cast<size_t>(n) * t.q.size() + (r - t.q.lo)) * window_row_floats();

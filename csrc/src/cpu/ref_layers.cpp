@@ -15,6 +15,14 @@
 
 namespace anx::cpu {
 
+void decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, const float* offset) {
+  int c = 0;
+  for (size_t i = 0; i < n; ++i) {
+    y[i] = std::fmaf(static_cast<float>(x[i]), scale[c], offset[c]);
+    c = c + 1 == C ? 0 : c + 1;
+  }
+}
+
 void conv2d(const float* x, const float* w, const float* b, float* y, int N, int H, int W, int C, int K, int F,
             int S, int P, int groups, bool relu, int pad_top, int pad_bottom) {
   const int pt = pad_top < 0 ? P : pad_top;

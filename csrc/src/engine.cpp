@@ -68,6 +68,10 @@ BlocksEngine::BlocksEngine(const BlockSpec& b1, const BlockSpec& b2, int H, int 
   if (b1.conv.P != 0) throw std::invalid_argument("conv1 padding must be 0 (row tiles read raw image rows)");
   if (d_.Hp2 <= 0 || d_.Wp2 <= 0) throw std::invalid_argument("input too small for AlexNet blocks 1-2");
   wq_ = d_.Wp1 + 2 * b2.conv.P;
+  if (d_.C0 <= hip::kU8MaxC) {
+    norm_.C = d_.C0;
+    for (int c = 0; c < d_.C0; ++c) norm_.sc[c] = 1.0f / 255.0f, norm_.of[c] = 0.f;
+  }
   {
     // a full image's worth of conv rows for the Auto crossover: what the whole-image tile computes (H1 / H2, or
     // one row less where the pool behind the conv drops the last row of an even map)
@@ -230,7 +234,8 @@ BlocksEngine::~BlocksEngine() {
                   static_cast<void*>(b2d_), static_cast<void*>(w1p_), static_cast<void*>(w2p_),
                   static_cast<void*>(koff1_), static_cast<void*>(koff2_), static_cast<void*>(c1_),
                   static_cast<void*>(q2_), static_cast<void*>(c2_), static_cast<void*>(u2w_),
-                  static_cast<void*>(wv_), static_cast<void*>(u1w_), static_cast<void*>(wv1_)})
+                  static_cast<void*>(wv_), static_cast<void*>(u1w_), static_cast<void*>(wv1_),
+                  static_cast<void*>(xdec_)})
     if (p) (void)hipFree(p);
 }
 
@@ -249,12 +254,52 @@ float* BlocksEngine::q2_row_ptr(const TilePlan& t, int n, int r) {
   return q2_ + static_cast<size_t>(n) * q2_image_stride_floats(t) + static_cast<size_t>(r - t.q.lo) * q2_row_floats();
 }
 
-hipError_t BlocksEngine::conv1_chunk(const float* xc, int n, const TilePlan& t, hipStream_t s, int c1_img0) {
+void BlocksEngine::set_input_norm(const float* scale, const float* offset) {
+  if (d_.C0 > hip::kU8MaxC) throw std::invalid_argument("byte input: too many input channels");
+  for (int c = 0; c < d_.C0; ++c) norm_.sc[c] = scale[c], norm_.of[c] = offset[c];
+}
+
+hipError_t BlocksEngine::decode_chunk(const uint8_t* x, size_t elems, hipStream_t s) {
+  if (norm_.C == 0) return hipErrorInvalidValue;
+  if (elems > xdec_cap_) {
+    // one launch chunk of whole images, once; a captured stream must not see the allocation
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
+      return hipErrorStreamCaptureUnsupported;
+    const size_t cap = static_cast<size_t>(chunk_) * d_.H * d_.W * d_.C0;
+    if (elems > cap) return hipErrorInvalidValue;
+    if (xdec_) ANX_TRY(hipFree(xdec_));
+    xdec_ = nullptr, xdec_cap_ = 0;
+    ANX_TRY(hipMalloc(reinterpret_cast<void**>(&xdec_), cap * sizeof(float)));
+    xdec_cap_ = cap;
+  }
+  return hip::decode_u8(x, xdec_, elems, norm_, s);
+}
+
+hipError_t BlocksEngine::conv1_chunk(In xin, int n, const TilePlan& t, hipStream_t s, int c1_img0) {
   RoctxRange rx("anx conv1");
   const ConvSpec& k1 = b1_.conv;
   const hip::OutView c1v{c1_ + static_cast<size_t>(c1_img0) * t.c1.size() * d_.W1 * d_.C1, t.c1.size(), d_.W1, d_.C1,
                          0, 0, 0};
-  if (impl_ == Impl::Mfma && wv1_ != nullptr && use_winograd(k_.conv1_algo, n, t.c1.size(), full1_)) {
+  const bool wino = impl_ == Impl::Mfma && wv1_ != nullptr && use_winograd(k_.conv1_algo, n, t.c1.size(), full1_);
+  const float* xc = xin.f32;
+  if (xin.u8 != nullptr) {
+    if (wino && k_.conv1_u8 && norm_.C == 3) {
+      const hip::Conv1WinoPlan w = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
+      if (hip::conv1_wino_one_kernel(w, c1v, k_)) {  // where the float path launches conv1_fused: the byte form
+        ANX_TRY(hip::conv1_fused_u8(w, xin.u8, norm_, u1w_, b1d_, c1v, true, s));
+        path_.conv1 = "fused";
+        input_ = "u8_fused";
+        return hipSuccess;
+      }
+    }
+    ANX_TRY(decode_chunk(xin.u8, static_cast<size_t>(n) * t.in.size() * d_.W * d_.C0, s));
+    xc = xdec_;
+    input_ = "u8_decode";
+  } else {
+    input_ = "f32";
+  }
+  if (wino) {
     const hip::Conv1WinoPlan w = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
     if (hip::conv1_wino_v_floats(w) > wv1_cap_) return hipErrorInvalidValue;
     bool one_kernel = false;  // set by the launcher where it picks the one-kernel form
@@ -275,6 +320,13 @@ hipError_t BlocksEngine::conv1_chunk(const float* xc, int n, const TilePlan& t, 
 }
 
 hipError_t BlocksEngine::stage1(const float* x, int N, const TilePlan& t, hipStream_t s, int n_lo, int n_hi) {
+  return stage1_in(In{x, nullptr}, N, t, s, n_lo, n_hi);
+}
+hipError_t BlocksEngine::stage1_u8(const uint8_t* x, int N, const TilePlan& t, hipStream_t s, int n_lo, int n_hi) {
+  return stage1_in(In{nullptr, x}, N, t, s, n_lo, n_hi);
+}
+
+hipError_t BlocksEngine::stage1_in(In x, int N, const TilePlan& t, hipStream_t s, int n_lo, int n_hi) {
   if (n_hi < 0) n_hi = N;
   if (N > max_batch_ || n_lo < 0 || n_hi > N) return hipErrorInvalidValue;
   if (t.out.empty()) return hipSuccess;
@@ -286,7 +338,7 @@ hipError_t BlocksEngine::stage1(const float* x, int N, const TilePlan& t, hipStr
   const int chunk = k_.chunk1 > 0 ? std::min(chunk_, k_.chunk1) : chunk_;
   for (int n0 = n_lo; n0 < n_hi; n0 += chunk) {
     const int n = std::min(chunk, n_hi - n0);
-    ANX_TRY(conv1_chunk(x + n0 * in_img, n, t, s));
+    ANX_TRY(conv1_chunk(x.at(n0 * in_img), n, t, s));
     RoctxRange rx("anx pool1");
     ANX_TRY(hip::maxpool(c1_, n, t.c1.size(), d_.W1, d_.C1, b1_.pool.F, b1_.pool.S,
                          hip::OutView{q2_ + n0 * q_img, t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, b2_.conv.P, 0}, s));
@@ -395,10 +447,17 @@ bool BlocksEngine::conv2_pools(const TilePlan& t) const {
 }
 
 hipError_t BlocksEngine::tile_forward(const float* x, int N, const TilePlan& t, float* y, hipStream_t s) {
+  return tile_forward_in(In{x, nullptr}, N, t, y, s);
+}
+hipError_t BlocksEngine::tile_forward_u8(const uint8_t* x, int N, const TilePlan& t, float* y, hipStream_t s) {
+  return tile_forward_in(In{nullptr, x}, N, t, y, s);
+}
+
+hipError_t BlocksEngine::tile_forward_in(In x, int N, const TilePlan& t, float* y, hipStream_t s) {
   if (N > max_batch_) return hipErrorInvalidValue;
   if (t.out.empty()) return hipSuccess;
   if (!fused_pool1(N, t)) {
-    ANX_TRY(stage1(x, N, t, s));
+    ANX_TRY(stage1_in(x, N, t, s, 0, -1));
     return stage2(N, t, y, s);
   }
   if (conv1_pools(N, t)) return tile_forward_conv1_pool(x, N, t, y, s);
@@ -416,7 +475,7 @@ hipError_t BlocksEngine::tile_forward(const float* x, int N, const TilePlan& t, 
     // sub-chunk keeps inside the Infinity Cache between the transform and the GEMM
     const int s1 = k_.conv1_sub > 0 ? std::min(n, k_.conv1_sub) : n;
     for (int a0 = 0; a0 < n; a0 += s1)
-      ANX_TRY(conv1_chunk(x + (n0 + a0) * in_img, std::min(s1, n - a0), t, s, a0));
+      ANX_TRY(conv1_chunk(x.at((n0 + a0) * in_img), std::min(s1, n - a0), t, s, a0));
     RoctxRange rx("anx pool1+conv2+pool2+lrn");
     const int s2 = k_.conv2_sub > 0 ? std::min(n, k_.conv2_sub) : n;
     for (int b0 = 0; b0 < n; b0 += s2) {
@@ -438,7 +497,7 @@ hipError_t BlocksEngine::tile_forward(const float* x, int N, const TilePlan& t, 
 // Whole images with pool1 in the one-kernel Conv1: conv1 + pool1 -> the conv2 window (+ the straddling
 // windows' partial maxima in c1_) -> merged input transform -> Winograd GEMM -> pool2 + LRN, per chunk.
 // The conv1 map never reaches HBM; bit-identical to the path above (max is exact in any order).
-hipError_t BlocksEngine::tile_forward_conv1_pool(const float* x, int N, const TilePlan& t, float* y, hipStream_t s) {
+hipError_t BlocksEngine::tile_forward_conv1_pool(In x, int N, const TilePlan& t, float* y, hipStream_t s) {
   const ConvSpec &k1 = b1_.conv, &k2 = b2_.conv;
   ANX_TRY(ensure_window(t, N, s));  // zero border once; every interior pixel is rewritten per call
   const size_t in_img = static_cast<size_t>(t.in.size()) * d_.W * d_.C0;
@@ -454,7 +513,19 @@ hipError_t BlocksEngine::tile_forward_conv1_pool(const float* x, int N, const Ti
       RoctxRange rx("anx conv1+pool1");
       const hip::Conv1WinoPlan w1 = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
       const hip::OutView win{q2_ + n0 * q_img, t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, k2.P, 0};
-      ANX_TRY(hip::conv1_fused_pool(w1, x + n0 * in_img, u1w_, b1d_, win, c1_, hp1, d_.Wp1, true, s, k_.conv1_fused - 1));
+      const In xc = x.at(n0 * in_img);
+      if (xc.u8 != nullptr && k_.conv1_u8 && norm_.C == 3) {
+        ANX_TRY(hip::conv1_fused_pool_u8(w1, xc.u8, norm_, u1w_, b1d_, win, c1_, hp1, d_.Wp1, true, s, k_.conv1_fused - 1));
+        input_ = "u8_fused";
+      } else {
+        const float* xf = xc.f32;
+        if (xc.u8 != nullptr) {
+          ANX_TRY(decode_chunk(xc.u8, static_cast<size_t>(n) * in_img, s));
+          xf = xdec_;
+        }
+        ANX_TRY(hip::conv1_fused_pool(w1, xf, u1w_, b1d_, win, c1_, hp1, d_.Wp1, true, s, k_.conv1_fused - 1));
+        input_ = xc.u8 != nullptr ? "u8_decode" : "f32";
+      }
       path_.conv1 = "fused_pool";
       path_.pool1 = "conv1_epilogue";
     }
@@ -501,6 +572,11 @@ hipError_t BlocksEngine::tile_forward_conv1_pool(const float* x, int N, const Ti
 hipError_t BlocksEngine::forward(const float* x, int N, float* y, hipStream_t s) {
   const DecompPlan p = make_plan(d_.H, d_.W, 1, Decomp::Overlap, b1_, b2_);
   return tile_forward(x, N, p.tiles[0], y, s);
+}
+
+hipError_t BlocksEngine::forward_u8(const uint8_t* x, int N, float* y, hipStream_t s) {
+  const DecompPlan p = make_plan(d_.H, d_.W, 1, Decomp::Overlap, b1_, b2_);
+  return tile_forward_u8(x, N, p.tiles[0], y, s);
 }
 
 }  // namespace anx

@@ -45,6 +45,7 @@ namespace {
 namespace w33 = anx::wino33;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
+using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 using lds_f32 = __attribute__((address_space(3))) float;
 using lds_void = __attribute__((address_space(3))) void;
 
@@ -97,7 +98,9 @@ constexpr int loads_at(int p) {
     if (p >= 0 && late_load_pt(u) == p) return u;
   return -1;
 }
-constexpr int x_ops(int p) { return p >= 0 && loads_at(p) >= 0 ? kN5 : 0; }
+// vector-memory ops of the X' row loaded at point p: one 8-B load per column of the fp32 image, two byte
+// loads per column of the byte image (per = 2)
+constexpr int x_ops(int p, int per = 1) { return p >= 0 && loads_at(p) >= 0 ? kN5 * per : 0; }
 static_assert(9 * kTiles * kOS <= kDummy, "epilogue scratch: nine position images below the dummy DMA slot");
 // pool1 epilogue: candidate pooled pixels are those whose window starts in tiles p0 - kPoolBack .. p0 + 31
 // (a window's tiles span at most tx + 1 raster indices: kPoolBack >= tx + 1, checked by the launcher)
@@ -128,11 +131,11 @@ __device__ __forceinline__ void sfor(F&& f) {
 __device__ __forceinline__ int swz(int row) { return (row >> 1) & 3; }
 
 struct Conv1FusedArgs {
-  const float* x;     // [N][Hin][W][3] image rows of the tile
+  const void* x;      // [N][Hin][W][3] image rows of the tile: float, or bytes (U8)
   const float* U;     // [25][96][48] transformed filters
   const float* bias;  // [96]
   OutView out;
-  int P, ty, tx, Ho, Wo, Hin, rowf;  // rowf = W * 3 floats per image row
+  int P, ty, tx, Ho, Wo, Hin, rowf;  // rowf = W * 3 elements per image row
   int xbytes, ubytes;                // buffer-resource extents (< 2^31)
   int n_ptiles, per_xcd;
   int relu;
@@ -143,12 +146,20 @@ struct Conv1FusedArgs {
   float* p1;
   int Hp, Wp;
   unsigned long long* dbg;  // ABL bit 64 (ANX_CONV1_PHASES diagnostics): per-workgroup stamps, else null
+  float sc[3], of[3];       // U8: a byte b of channel c decodes to fmaf(float(b), sc[c], of[c])
 };
 
 // UM: where U lives -- 0 the shared 3-slot LDS ring (every wave's DMA, a barrier per point), 1 a private
 // 2-slot LDS ring per wave (own DMA, own vmcnt; barriers only at a-step starts), 2 registers (each wave loads
 // its B fragments from L2 one point ahead; no U in LDS at all)
-template <bool POOL, int ABL = 0, int UM = 0>
+//
+// U8: the image is bytes. Only the X' loader differs: each (u, v) pair is two byte loads (any address is
+// aligned for a byte; the range check is per byte, so the buffer's last byte loads although nothing follows
+// it), kept raw in registers like the fp32 rows and decoded in place where t_add first consumes them. A
+// position outside the image decodes to 0, not to of[c]: the fp32 kernel reads zeros there. Everything after
+// the decode is the fp32 kernel's arithmetic, so the output equals decode_u8 + the fp32 kernel bit for bit.
+// Measured slower than decode_u8 + the fp32 kernel inside the two-lane step (knob conv1_u8, default 0).
+template <bool POOL, int ABL = 0, int UM = 0, bool U8 = false>
 __global__ void __launch_bounds__(kNT, 3) conv1_fused_kernel(Conv1FusedArgs a) {
   // (two accumulation chains per point, odd k-steps on the second, measured slower with the per-wave ring:
   // main loop 48.5 k vs 44.2 k clk, profiles/r06_conv1_upw/)
@@ -169,7 +180,7 @@ __global__ void __launch_bounds__(kNT, 3) conv1_fused_kernel(Conv1FusedArgs a) {
     rt0 = __builtin_amdgcn_s_memrealtime();
   }
 #if __HIP_DEVICE_COMPILE__
-  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, a.xbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, a.xbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t ur = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.U), 0, a.ubytes, 0x00020000);
 #endif
   lds_f32* lds3 = (lds_f32*)(lds);
@@ -239,7 +250,9 @@ __global__ void __launch_bounds__(kNT, 3) conv1_fused_kernel(Conv1FusedArgs a) {
   }
   const int row0 = bti * kPitch + rh;               // image row of u = 0 (this slot's phase row)
   const int col0 = btj * kPitch * 3 + bf2;          // float of v = 0 inside the row
-  [[maybe_unused]] const int xoff = ((bn * a.Hin + row0) * a.rowf + col0) * 4;
+  constexpr int kEl = U8 ? 1 : 4;  // bytes per image element
+  constexpr int kXO = U8 ? 2 : 1;  // vector-memory ops per (u, v) pair
+  [[maybe_unused]] const int xoff = ((bn * a.Hin + row0) * a.rowf + col0) * kEl;
   // X'[u][v] (2 channels): image row 12 ti + 4u + rh, floats (12 tj + 4v) * 3 + bf2 .. +1 (zero outside).
   // Every load is issued by every lane (a lane outside the image reads past the buffer's extent, which
   // returns 0), so each X' row is exactly kN5 vector-memory ops per wave and the schedule's vmcnt
@@ -255,14 +268,44 @@ __global__ void __launch_bounds__(kNT, 3) conv1_fused_kernel(Conv1FusedArgs a) {
     offv[i] = o < a.rowf ? xoff : kOOB;
     cpart[i] = o + 1 == a.rowf;
   }
+  // U8: the pair's bytes, zero-extended, in the bits of the two floats until decode_row turns them into floats
   auto load_x = [&](int u, int v) -> f32x2 {
     f32x2 d = {0.f, 0.f};
-    if constexpr ((ABL & 1) != 0) return f32x2{static_cast<float>(offv[v] + u), static_cast<float>(v)};
+    if constexpr ((ABL & 1) != 0 && !U8) return f32x2{static_cast<float>(offv[v] + u), static_cast<float>(v)};
 #if __HIP_DEVICE_COMPILE__
-    const int so = (kPh * u * a.rowf + 12 * v) * 4;
-    d = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(xr, rok[u] ? offv[v] : kOOB, so, 0));
+    const int so = (kPh * u * a.rowf + 12 * v) * kEl;
+    const int vo = rok[u] ? offv[v] : kOOB;
+    if constexpr (U8) {
+      // the pair's second byte has its own range check: past the buffer's last byte it alone reads 0
+      d = __builtin_bit_cast(f32x2, u32x2{__builtin_amdgcn_raw_buffer_load_b8(xr, vo, so, 0),
+                                          __builtin_amdgcn_raw_buffer_load_b8(xr, vo + 1, so, 0)});
+    } else {
+      d = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(xr, vo, so, 0));
+    }
 #endif
     return d;
+  };
+  // U8: this thread's two channels are fixed (col0 + 12 v is constant mod 3): their (scale, offset) pairs
+  [[maybe_unused]] float dsx = 0.f, dox = 0.f, dsy = 0.f, doy = 0.f;
+  if constexpr (U8) {
+    const int c0 = bf2 % 3, c1 = (bf2 + 1) % 3;
+    dsx = c0 == 0 ? a.sc[0] : c0 == 1 ? a.sc[1] : a.sc[2];
+    dox = c0 == 0 ? a.of[0] : c0 == 1 ? a.of[1] : a.of[2];
+    dsy = c1 == 0 ? a.sc[0] : c1 == 1 ? a.sc[1] : a.sc[2];
+    doy = c1 == 0 ? a.of[0] : c1 == 1 ? a.of[1] : a.of[2];
+  }
+  // U8: X' row u from bytes to floats, in place, ONCE, where the row is first consumed (the loads stay in
+  // flight until then; every later V_a that takes the row reads the floats). A pair outside the image (row past
+  // Hin, column past the row, no tile) is 0 AFTER decoding. The .y of the row's last element (cpart) decodes
+  // to something finite and is zeroed in t by v_store, like the fp32 form's.
+  [[maybe_unused]] auto decode_row = [&](int u, f32x2 (&r)[kN5]) {
+#pragma unroll
+    for (int v = 0; v < kN5; ++v) {
+      const bool in = rok[u] && offv[v] != kOOB;
+      const u32x2 raw = __builtin_bit_cast(u32x2, r[v]);
+      r[v].x = in ? __builtin_fmaf(static_cast<float>(raw.x), dsx, dox) : 0.f;
+      r[v].y = in ? __builtin_fmaf(static_cast<float>(raw.y), dsy, doy) : 0.f;
+    }
   };
   f32x2 t[kN5];
   auto t_zero = [&]() {
@@ -336,7 +379,10 @@ __global__ void __launch_bounds__(kNT, 3) conv1_fused_kernel(Conv1FusedArgs a) {
   });
   sfor<0, kN5>([&](auto Uc) {
     constexpr int u = decltype(Uc)::value;
-    if constexpr (prologue_row(u)) t_add(std::integral_constant<int, 0>{}, Uc, xrow[u]);
+    if constexpr (prologue_row(u)) {
+      if constexpr (U8) decode_row(u, xrow[u]);
+      t_add(std::integral_constant<int, 0>{}, Uc, xrow[u]);
+    }
   });
   v_store(0);
   t_zero();
@@ -351,9 +397,9 @@ __global__ void __launch_bounds__(kNT, 3) conv1_fused_kernel(Conv1FusedArgs a) {
       constexpr int b = decltype(Bc)::value, p = av * kN5 + b;
       // in flight past this barrier: the ops issued after U_p (at point p - 2: its X' row, if any; at
       // point p - 1: U_{p+1} and its X' row): this wave's U_p has landed, X' rows finish on their own
-      constexpr int inflight = (p + 1 < kPts ? 2 : 0) + x_ops(p - 1) + x_ops(p - 2);
+      constexpr int inflight = (p + 1 < kPts ? 2 : 0) + x_ops(p - 1, kXO) + x_ops(p - 2, kXO);
       // UPW: U_p was issued at point p - 1 (the prologue for p = 0); after it only point p - 1's X' row loads
-      constexpr int inflight_w = x_ops(p - 1);
+      constexpr int inflight_w = x_ops(p - 1, kXO);
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (UREG) {
         if constexpr (b == 0) lds_barrier<-1>();  // V_a published; U is in registers (the compiler waits for it)
@@ -410,6 +456,8 @@ __global__ void __launch_bounds__(kNT, 3) conv1_fused_kernel(Conv1FusedArgs a) {
 #pragma unroll
         for (int v = 0; v < kN5; ++v) asm volatile("" ::"v"(xrow[b][v]));
       } else if constexpr (needs_row(av + 1, b)) {
+        // a row loaded in the main loop is first consumed here, by V_{first_a}
+        if constexpr (U8 && !prologue_row(b) && first_a(b) == av + 1) decode_row(b, xrow[b]);
         t_add(std::integral_constant<int, av + 1>{}, Bc, xrow[b]);
 #pragma unroll
         for (int v = 0; v < kN5; ++v) asm volatile("" : "+v"(t[v]));
@@ -618,13 +666,18 @@ void conv1_phase_report(const std::vector<unsigned long long>& h, int n) {
                median(life), median(gaps), gaps.size());
 }
 
-hipError_t conv1_fused_launch(const Conv1WinoPlan& w, const float* x, const float* U, const float* bias, OutView out,
-                              bool relu, hipStream_t s, float* p1, int Hp, int Wp, int um = 0) {
+// nm != nullptr: x is a byte image decoded with *nm (the U8 instantiations), else floats
+hipError_t conv1_fused_launch(const Conv1WinoPlan& w, const void* x, const float* U, const float* bias, OutView out,
+                              bool relu, hipStream_t s, float* p1, int Hp, int Wp, int um = 0, const U8Norm* nm = nullptr) {
   static const hipError_t attr = [] {
     for (const void* k : {reinterpret_cast<const void*>(conv1_fused_kernel<false>),
                           reinterpret_cast<const void*>(conv1_fused_kernel<true>),
                           reinterpret_cast<const void*>(conv1_fused_kernel<true, 0, 1>),
-                          reinterpret_cast<const void*>(conv1_fused_kernel<true, 0, 2>)}) {
+                          reinterpret_cast<const void*>(conv1_fused_kernel<true, 0, 2>),
+                          reinterpret_cast<const void*>(conv1_fused_kernel<false, 0, 0, true>),
+                          reinterpret_cast<const void*>(conv1_fused_kernel<true, 0, 0, true>),
+                          reinterpret_cast<const void*>(conv1_fused_kernel<true, 0, 1, true>),
+                          reinterpret_cast<const void*>(conv1_fused_kernel<true, 0, 2, true>)}) {
       const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e != hipSuccess) return e;
     }
@@ -643,7 +696,11 @@ hipError_t conv1_fused_launch(const Conv1WinoPlan& w, const float* x, const floa
   a.Wo = w.W1;
   a.Hin = w.Hin;
   a.rowf = w.W * 3;
-  a.xbytes = static_cast<int>(static_cast<long>(w.N) * w.Hin * w.W * 3 * 4);
+  a.xbytes = static_cast<int>(static_cast<long>(w.N) * w.Hin * w.W * 3 * (nm ? 1 : 4));  // the image, not a byte more
+  if (nm != nullptr) {
+    if (nm->C != 3) return hipErrorInvalidValue;
+    for (int c = 0; c < 3; ++c) a.sc[c] = nm->sc[c], a.of[c] = nm->of[c];
+  }
   a.ubytes = kPts * kK * kCh * 4;
   a.n_ptiles = (w.P + kTiles - 1) / kTiles;
   a.per_xcd = (a.n_ptiles + 7) / 8;
@@ -652,6 +709,17 @@ hipError_t conv1_fused_launch(const Conv1WinoPlan& w, const float* x, const floa
   a.Hp = Hp;
   a.Wp = Wp;
   const unsigned grid = static_cast<unsigned>(a.per_xcd * 8);
+  if (nm != nullptr) {  // byte image: the four production forms (no probe / diagnostic builds)
+    if (p1 != nullptr && um == 1)
+      conv1_fused_kernel<true, 0, 1, true><<<grid, kNT, kLdsW, s>>>(a);
+    else if (p1 != nullptr && um == 2)
+      conv1_fused_kernel<true, 0, 2, true><<<grid, kNT, kLds, s>>>(a);
+    else if (p1 != nullptr)
+      conv1_fused_kernel<true, 0, 0, true><<<grid, kNT, kLds, s>>>(a);
+    else
+      conv1_fused_kernel<false, 0, 0, true><<<grid, kNT, kLds, s>>>(a);
+    return hipGetLastError();
+  }
 #ifdef ANX_CONV1_ABL  // cost-probe builds only (CMake ANX_CONV1_ABL=ON): ANX_CONV1_ABL=<bits> picks the probe
   static const int abl = [] {
     const char* e = std::getenv("ANX_CONV1_ABL");
@@ -712,7 +780,6 @@ hipError_t conv1_fused_launch(const Conv1WinoPlan& w, const float* x, const floa
     conv1_fused_kernel<true, 0, 1><<<grid, kNT, kLdsW, s>>>(a);
   else if (p1 != nullptr && um == 2)
     conv1_fused_kernel<true, 0, 2><<<grid, kNT, kLds, s>>>(a);
-
   else if (p1 != nullptr)
     conv1_fused_kernel<true><<<grid, kNT, kLds, s>>>(a);
   else
@@ -742,6 +809,21 @@ hipError_t conv1_fused_pool(const Conv1WinoPlan& w, const float* x, const float*
   if (w.P == 0 || w.H1 <= 0 || w.W1 <= 0) return hipSuccess;
   if (p1 == nullptr || !conv1_fused_pool_eligible(w, window, Hp, Wp)) return hipErrorInvalidValue;
   return conv1_fused_launch(w, x, U, bias, window, relu, s, p1, Hp, Wp, um);
+}
+
+hipError_t conv1_fused_u8(const Conv1WinoPlan& w, const uint8_t* x, const U8Norm& nm, const float* U, const float* bias,
+                          OutView out, bool relu, hipStream_t s) {
+  if (w.P == 0 || w.H1 <= 0 || w.W1 <= 0) return hipSuccess;
+  if (!conv1_fused_eligible(w, out)) return hipErrorInvalidValue;
+  return conv1_fused_launch(w, x, U, bias, out, relu, s, nullptr, 0, 0, 0, &nm);
+}
+
+hipError_t conv1_fused_pool_u8(const Conv1WinoPlan& w, const uint8_t* x, const U8Norm& nm, const float* U,
+                               const float* bias, OutView window, float* p1, int Hp, int Wp, bool relu, hipStream_t s,
+                               int um) {
+  if (w.P == 0 || w.H1 <= 0 || w.W1 <= 0) return hipSuccess;
+  if (p1 == nullptr || !conv1_fused_pool_eligible(w, window, Hp, Wp)) return hipErrorInvalidValue;
+  return conv1_fused_launch(w, x, U, bias, window, relu, s, p1, Hp, Wp, um, &nm);
 }
 
 }  // namespace anx::hip

@@ -245,9 +245,13 @@ void conv1_wino_weights_host(int K, int F, const float* w_kcff, std::vector<floa
     }
 }
 
+bool conv1_wino_one_kernel(const Conv1WinoPlan& w, const OutView& out, const Knobs& kn) {
+  return kn.conv1_fused && conv1_fused_eligible(w, out);
+}
+
 hipError_t conv1_wino(const Conv1WinoPlan& w, const float* x, float* V, const float* U, const float* bias, OutView out,
                       bool relu, hipStream_t s, const Knobs& kn, bool* one_kernel) {
-  const bool fused = kn.conv1_fused && conv1_fused_eligible(w, out);
+  const bool fused = conv1_wino_one_kernel(w, out, kn);
   if (one_kernel) *one_kernel = fused;
   if (w.P == 0 || w.H1 <= 0 || w.W1 <= 0) return hipSuccess;
   if (fused) return conv1_fused(w, x, U, bias, out, relu, s);

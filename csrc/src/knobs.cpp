@@ -39,6 +39,7 @@ const Field kFields[] = {
     {"fuse_pool1", &Knobs::fuse_pool1, nullptr, 0, 1, "ANX_FUSE_POOL1"},
     {"conv1_fused", &Knobs::conv1_fused, nullptr, 0, 3, "ANX_CONV1_FUSED"},
     {"conv1_pool", &Knobs::conv1_pool, nullptr, 0, 1, "ANX_CONV1_POOL"},
+    {"conv1_u8", &Knobs::conv1_u8, nullptr, 0, 1, "ANX_CONV1_U8"},
     {"conv1_sub", &Knobs::conv1_sub, nullptr, 0, 1 << 30, "ANX_CONV1_SUB"},
     {"conv2_sub", &Knobs::conv2_sub, nullptr, 0, 1 << 30, "ANX_CONV2_SUB"},
     {"conv2_pool", &Knobs::conv2_pool, nullptr, 0, 1, "ANX_CONV2_POOL"},

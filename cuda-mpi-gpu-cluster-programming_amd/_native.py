@@ -74,6 +74,17 @@ _SIGS = {
     "anx_engine_stage1": (_I, [_P, _P, _I, C.POINTER(TileC), _P]),
     "anx_engine_stage2": (_I, [_P, _I, C.POINTER(TileC), _P, _P]),
     "anx_engine_window": (_I, [_P, C.POINTER(TileC), _I, _I, C.POINTER(_P), C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "anx_engine_set_input_norm": (_I, [_P, _P, _P]),
+    "anx_engine_forward_u8": (_I, [_P, _P, _I, _P, _P]),
+    "anx_engine_tile_forward_u8": (_I, [_P, _P, _I, C.POINTER(TileC), _P, _P]),
+    "anx_engine_stage1_u8": (_I, [_P, _P, _I, C.POINTER(TileC), _P]),
+    "anx_engine_last_input": (_I, [_P, C.c_char_p, _SZ]),
+    "anx_decode_u8": (_I, [_P, _P, _SZ, _I, _P, _P, _P]),
+    "anx_cpu_decode_u8": (_I, [_P, _P, _SZ, _I, _P, _P]),
+    "anx_cpu_engine_set_input_norm": (_I, [_P, _P, _P]),
+    "anx_cpu_engine_forward_u8": (_I, [_P, _P, _I, _P]),
+    "anx_cpu_engine_tile_forward_u8": (_I, [_P, _P, _I, C.POINTER(TileC), _P]),
+    "anx_cpu_engine_stage1_u8": (_I, [_P, _P, _I, C.POINTER(TileC)]),
     "anx_cpu_engine_create": (_I, [C.POINTER(_P), C.POINTER(BlockC), C.POINTER(BlockC), _I, _I, _P, _P, _P, _P]),
     "anx_cpu_engine_destroy": (_I, [_P]),
     "anx_cpu_engine_tile_forward": (_I, [_P, _P, _I, C.POINTER(TileC), _P]),

@@ -21,6 +21,17 @@ forwards: the lanes are not joined per call but run free on their own streams, s
 forward apart, so one lane's HBM-bound kernels overlap the other's GEMMs in steady state
 (``profiles/r02_lanes_async.txt``: 128 images 0.629 -> 0.561 ms per forward). On the CPU it runs libanx's C++ host engine (CpuBlocks). There is no eager-PyTorch
 fallback: the PyTorch oracle lives in :mod:`anx.models.reference` and is only used by tests.
+
+Byte images: every entry point that takes the image (``forward``, ``forward_async``, ``tile_forward``,
+``stage1``) also takes a contiguous ``torch.uint8`` tensor of the same shape. A byte ``b`` of channel ``c``
+means ``fmaf(float(b), scale[c], offset[c])`` in fp32 (:func:`anx.ops.decode_u8`), with ``scale = 1/255`` and
+``offset = 0`` unless ``input_norm=(mean, std)`` (0-255 pixel units) sets ``scale = 1/std``,
+``offset = -mean/std``. The output equals the float entry point fed the decoded image bit for bit. On the GPU
+the launch chunk is decoded into a workspace (allocated by the first call that needs it: warm up once before
+capturing a graph) and the float kernels run on it; with knob ``conv1_u8=1`` the one-kernel Conv1 loads the
+bytes itself and no float copy of the input exists on the device (measured slower in the two-lane step, so
+not the default: ``profiles/u8_input/``). The reference has no byte input (every version fills
+float arrays, v1_serial/src/main.cpp:18-43).
 """
 from __future__ import annotations
 
@@ -47,6 +58,32 @@ def split_lanes(n: int, lanes: int) -> list[int]:
     return [n * i // lanes for i in range(lanes + 1)]
 
 
+def norm_scale_offset(input_norm, channels: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(mean, std)`` in 0-255 pixel units -> fp32 ``(scale, offset)`` = ``(1/std, -mean/std)``, computed in
+    fp64 and rounded once. ``None`` -> ``(1/255, 0)``. Each of mean / std is a number or ``channels`` numbers."""
+    if input_norm is None:
+        return (torch.full((channels,), 1.0 / 255.0, dtype=torch.float64).to(torch.float32),
+                torch.zeros(channels, dtype=torch.float32))
+    try:
+        mean, std = input_norm
+        mean = torch.as_tensor(mean, dtype=torch.float64).reshape(-1)
+        std = torch.as_tensor(std, dtype=torch.float64).reshape(-1)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"input_norm must be (mean, std) of numbers: {e}") from e
+    if mean.numel() == 1:
+        mean = mean.expand(channels)
+    if std.numel() == 1:
+        std = std.expand(channels)
+    if mean.numel() != channels or std.numel() != channels:
+        raise ValueError(f"input_norm: mean and std need 1 or {channels} values each")
+    if not bool(torch.isfinite(mean).all()) or not bool(torch.isfinite(std).all()) or bool((std <= 0).any()):
+        raise ValueError("input_norm: mean must be finite and std finite and > 0")
+    scale, offset = (1.0 / std).to(torch.float32), (-mean / std).to(torch.float32)
+    if not bool(torch.isfinite(scale).all()) or not bool(torch.isfinite(offset).all()):
+        raise ValueError("input_norm: 1/std or mean/std overflows float32")
+    return scale.contiguous(), offset.contiguous()
+
+
 def _tile_c(t: TilePlan) -> nat.TileC:
     return nat.TileC(t.inp.lo, t.inp.hi, t.c1.lo, t.c1.hi, t.p1.lo, t.p1.hi, t.q.lo, t.q.hi, t.c2.lo, t.c2.hi,
                      t.out.lo, t.out.hi)
@@ -69,7 +106,7 @@ class AlexNetBlocks:
     def __init__(self, weights: dict | None = None, *, init: str = "const", seed: int = 0, lrn_mode: str = "div_n",
                  groups2: int = 1, H: int = IN_H, W: int = IN_W, device="cuda", impl: str = "mfma",
                  max_batch: int = 1, specs: tuple[BlockSpec, BlockSpec] | None = None, lanes: int = 1,
-                 knobs: dict | None = None, lane_priority: int = 0):
+                 knobs: dict | None = None, lane_priority: int = 0, input_norm=None):
         self.b1, self.b2 = specs if specs is not None else blocks(lrn_mode, groups2)
         if self.b1.has_lrn:
             raise ValueError("the native engine implements LRN after block 2 only (the reference's topology)")
@@ -87,6 +124,9 @@ class AlexNetBlocks:
         self.impl = impl
         # kernel knobs of this model's engines (anx.utils.tuning): applied at every engine creation
         self.knobs = {k: knob_value(k, v) for k, v in (knobs or {}).items()}
+        # byte input: (mean, std) in 0-255 pixel units as given, and the fp32 (scale, offset) every engine gets
+        self.input_norm = input_norm
+        self._norm = norm_scale_offset(input_norm, self.dims.C0)
         self._engine = None
         self._cap = 0
         if lanes < 1:
@@ -102,7 +142,8 @@ class AlexNetBlocks:
             _check_hw_queues(lanes)
             for _ in range(lanes - 1):
                 self._lanes.append(AlexNetBlocks(self.weights, specs=(self.b1, self.b2), H=H, W=W, device=self.device,
-                                                 impl=impl, max_batch=per_lane, knobs=self.knobs))
+                                                 impl=impl, max_batch=per_lane, knobs=self.knobs,
+                                                 input_norm=input_norm))
                 # lane_priority < 0: side lanes on high-priority streams (their waves dispatch first)
                 self._lane_streams.append(torch.cuda.Stream(self.device, priority=lane_priority))
         self._own_stream = None  # lane 0's stream in forward_async (the joined forward uses the current one)
@@ -125,6 +166,41 @@ class AlexNetBlocks:
         self.knobs[name] = v
         for m in self._lanes:
             m.set_knob(name, v)
+
+    def set_input_norm(self, mean=None, std=None) -> None:
+        """Meaning of byte input from now on (every lane): ``(mean, std)`` in 0-255 pixel units, a number or one
+        per channel each; no arguments: back to ``byte / 255``."""
+        if (mean is None) != (std is None):
+            raise ValueError("set_input_norm takes both mean and std, or neither")
+        norm = None if mean is None else (mean, std)
+        self._norm = norm_scale_offset(norm, self.dims.C0)
+        self.input_norm = norm
+        self._apply_norm()
+        for m in self._lanes:
+            m.set_input_norm(mean, std)
+
+    def _apply_norm(self) -> None:
+        if self._engine is not None:
+            fn = "anx_engine_set_input_norm" if self.is_cuda else "anx_cpu_engine_set_input_norm"
+            nat.call(fn, self._engine, self._norm[0].data_ptr(), self._norm[1].data_ptr())
+
+    def decode_u8(self, x: torch.Tensor) -> torch.Tensor:
+        """The float32 image this model's byte input means (:func:`anx.ops.decode_u8` with its scale / offset)."""
+        from ..ops import decode_u8
+        return decode_u8(x, self._norm[0], self._norm[1])
+
+    def last_input(self, lane: int = 0) -> str | None:
+        """How the last forward / tile_forward / stage1 of this model's GPU engine (``lane`` > 0: that side
+        lane's) fed Conv1: ``"f32"`` (float input), ``"u8_fused"`` (the one-kernel Conv1 loaded the bytes),
+        ``"u8_decode"`` (decode kernel, then the float path); ``None`` before the first. Recorded at the launch;
+        reading it makes no device call."""
+        if not self.is_cuda:
+            raise ValueError("last_input belongs to the GPU engine")
+        if lane:
+            return self._lanes[lane - 1].last_input()
+        buf = C.create_string_buffer(32)
+        nat.call("anx_engine_last_input", self._engine, buf, len(buf))
+        return buf.value.decode() or None
 
     def get_knob(self, name: str) -> int:
         """The value the GPU engine launches with."""
@@ -167,6 +243,7 @@ class AlexNetBlocks:
         else:
             nat.call("anx_cpu_engine_create", C.byref(h), *args)
         self._engine, self._cap = h, max(1, n)
+        self._apply_norm()
 
     def close(self) -> None:
         for m in getattr(self, "_lanes", ()):
@@ -196,8 +273,8 @@ class AlexNetBlocks:
     def _check_in(self, x: torch.Tensor, rows: int) -> int:
         if x.dim() != 4 or tuple(x.shape[1:]) != (rows, self.W, self.dims.C0):
             raise ValueError(f"expected NHWC input [N,{rows},{self.W},{self.dims.C0}], got {tuple(x.shape)}")
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            raise ValueError("input must be contiguous float32")
+        if x.dtype not in (torch.float32, torch.uint8) or not x.is_contiguous():
+            raise ValueError("input must be contiguous float32 (or uint8: byte images)")
         if x.device != self.device:
             raise ValueError(f"input on {x.device}, model on {self.device}")
         return x.shape[0]
@@ -319,11 +396,12 @@ class AlexNetBlocks:
         if tile.out.size == 0 or N == 0:
             return y
         self._ensure(N)
+        u8 = "_u8" if x.dtype == torch.uint8 else ""
         if self.is_cuda:
-            nat.call("anx_engine_tile_forward", self._engine, x.data_ptr(), N, C.byref(_tile_c(tile)), y.data_ptr(),
-                     self._stream())
+            nat.call("anx_engine_tile_forward" + u8, self._engine, x.data_ptr(), N, C.byref(_tile_c(tile)),
+                     y.data_ptr(), self._stream())
         else:
-            nat.call("anx_cpu_engine_tile_forward", self._engine, x.data_ptr(), N, C.byref(_tile_c(tile)),
+            nat.call("anx_cpu_engine_tile_forward" + u8, self._engine, x.data_ptr(), N, C.byref(_tile_c(tile)),
                      y.data_ptr())
         return y
 
@@ -331,10 +409,11 @@ class AlexNetBlocks:
         """conv1+ReLU+pool1 of input rows ``tile.inp`` into the conv2 input window (rows tile.p1)."""
         N = self._check_in(x, tile.inp.size)
         self._ensure(N)
+        u8 = "_u8" if x.dtype == torch.uint8 else ""
         if self.is_cuda:
-            nat.call("anx_engine_stage1", self._engine, x.data_ptr(), N, C.byref(_tile_c(tile)), self._stream())
+            nat.call("anx_engine_stage1" + u8, self._engine, x.data_ptr(), N, C.byref(_tile_c(tile)), self._stream())
         else:
-            nat.call("anx_cpu_engine_stage1", self._engine, x.data_ptr(), N, C.byref(_tile_c(tile)))
+            nat.call("anx_cpu_engine_stage1" + u8, self._engine, x.data_ptr(), N, C.byref(_tile_c(tile)))
 
     def stage2(self, N: int, tile: TilePlan, out: torch.Tensor | None = None) -> torch.Tensor:
         """conv2+ReLU+pool2+LRN of the (halo-completed) window -> output rows ``tile.out``."""

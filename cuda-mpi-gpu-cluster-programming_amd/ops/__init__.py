@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from .. import _native as nat
 from ..config import conv_out_dim, pool_out_dim
 
-__all__ = ["conv2d", "relu", "maxpool", "lrn", "maxpool_lrn", "clear_cache"]
+__all__ = ["conv2d", "relu", "maxpool", "lrn", "maxpool_lrn", "decode_u8", "clear_cache"]
 
 _LRN_MODES = {"div_n": 0, "raw": 1}
 _pack_cache: dict = {}
@@ -109,6 +109,31 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None, stri
     nat.call("anx_conv2d_mfma", plan, nat.ptr(xp), nat.ptr(packed), nat.ptr(koff), nat.ptr(bias), nat.ptr(out),
              Ho, Wo, out.shape[3], 0, 0, c_off, int(relu), s)
     return out
+
+
+def decode_u8(x: torch.Tensor, scale=None, offset=None) -> torch.Tensor:
+    """Byte image -> float32, the meaning of byte input everywhere in the package: element i (flat index) becomes
+    ``fmaf(float(x[i]), scale[i % C], offset[i % C])``, one fused multiply-add in fp32, with C the number of
+    scale values (default: ``scale = 1/255`` and ``offset = 0`` for each of the ``x.shape[-1]`` channels).
+    ``x`` is a contiguous uint8 tensor that may start at any byte of its storage (a slice); the result has its
+    shape. The reference has no byte input."""
+    if x.dtype != torch.uint8 or not x.is_contiguous():
+        raise ValueError("decode_u8: expected a contiguous uint8 tensor")
+    Cn = x.shape[-1] if x.dim() > 1 else 1
+    sc = torch.full((Cn,), 1.0 / 255.0, dtype=torch.float64) if scale is None else torch.as_tensor(scale, dtype=torch.float64).reshape(-1)
+    of = torch.zeros_like(sc) if offset is None else torch.as_tensor(offset, dtype=torch.float64).reshape(-1)
+    if sc.numel() != of.numel() or sc.numel() < 1 or (x.is_cuda and sc.numel() > 16):
+        raise ValueError("decode_u8: scale and offset need the same number of values (1 to 16 on the GPU)")
+    sc, of = sc.to("cpu", torch.float32).contiguous(), of.to("cpu", torch.float32).contiguous()
+    y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    if x.numel() == 0:
+        return y
+    if x.is_cuda:
+        nat.call("anx_decode_u8", x.data_ptr(), y.data_ptr(), x.numel(), sc.numel(), sc.data_ptr(), of.data_ptr(),
+                 nat.stream_ptr(x.device))
+    else:
+        nat.call("anx_cpu_decode_u8", x.data_ptr(), y.data_ptr(), x.numel(), sc.numel(), sc.data_ptr(), of.data_ptr())
+    return y
 
 
 def relu(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
