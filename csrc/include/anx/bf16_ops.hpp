@@ -43,8 +43,11 @@ hipError_t splitk_reduce_bf16(const float* ws, int ksplit, int M, int K, const f
 // out_f32 != nullptr: write fp32 (contiguous [M][K]) instead of the bf16 view (final logits).
 // glds (Knobs::bf16_glds): 128x128 vec8 layers (conv2-5, FC) run the LDS-DMA ring with 2 (default) or
 // 3 slots, 0 = the register-staged kernel (A/B).
+// ran_slots (optional): set at the launch to the kernel that ran, 2 / 3 = the LDS-DMA ring with that many
+// slots, 0 = the register-staged kernel of p.variant.
 hipError_t conv2d_bf16(const ConvPlanB& p, const void* x, const void* wpacked, const int* koff, const float* bias,
-                       OutViewB out, float* out_f32, bool relu, hipStream_t s, SplitK split = {}, int glds = 2);
+                       OutViewB out, float* out_f32, bool relu, hipStream_t s, SplitK split = {}, int glds = 2,
+                       int* ran_slots = nullptr);
 // Wide-tile kernel (conv_bf16_big.hip): 1 workgroup per CU, 8 waves over a 256-row tile, LDS-DMA
 // double buffer, 16x16x32 MFMA, LDS-transposed epilogue with 16-B stores. Same packed weights / koff
 // as conv2d_bf16 (vec8, non-taps8 plans; the koff table is recomputed in arithmetic); bf16 output
@@ -60,9 +63,11 @@ bool conv_bf16_big_ok(const ConvPlanB& p, int cfg, const OutViewB& out);
 int pick_bf16_big_cfg(const ConvPlanB& p, const OutViewB& out, int cus = 256);
 // split.ws set (groups == 1): fp32 partial slabs [ksplit][M][Kg] into split.ws, K split ksplit ways
 // (no bias / ReLU; then splitk_reduce_bf16, which also serves an fp32 result at ksplit 1). `out` is
-// then only validated.
+// then only validated. ran_cfg (optional): set at the launch to the config that ran (a ping-pong config asked
+// for slabs runs as its plain twin).
 hipError_t conv2d_bf16_big(const ConvPlanB& p, int cfg, const void* x, const void* wpacked, const int* koff,
-                           const float* bias, OutViewB out, bool relu, hipStream_t s, SplitK split = {});
+                           const float* bias, OutViewB out, bool relu, hipStream_t s, SplitK split = {},
+                           int* ran_cfg = nullptr);
 // Fully-connected layer plan on the wide-tile kernel (cfg -1: not applicable).
 struct BigFc {
   int cfg, ksplit;
@@ -89,8 +94,15 @@ size_t conv1_ring_weight_bytes();
 // pool_out: also max-pool 3x3/2 into this 27x27x96 view (pool1). With f32_input and one workgroup
 // per image (N >= cus) the pool runs in the kernel's epilogue and `out` is NOT written (the 55x55
 // map never reaches HBM); otherwise Conv1 writes `out` (dense 55x55x96) and maxpool_bf16 follows.
+// ran (optional): set at the launch to the segment count (workgroups per image) and whether pool1 ran in the
+// kernel's epilogue.
+struct RingRan {
+  int segs = 0;
+  bool pool = false;
+};
 hipError_t conv1_bf16_ring(const void* x, int N, const void* wpacked, const float* bias, OutViewB out, bool relu,
-                           hipStream_t s, int cus = 256, bool f32_input = false, const OutViewB* pool_out = nullptr);
+                           hipStream_t s, int cus = 256, bool f32_input = false, const OutViewB* pool_out = nullptr,
+                           RingRan* ran = nullptr);
 
 }  // namespace hip
 
@@ -102,6 +114,22 @@ struct FullWeights {
   std::vector<float> w[8], b[8];
 };
 void full_weight_shapes(int classes, int groups2, size_t wn[8], size_t bn[8]);
+
+// Which kernels FullEngine's last forward launched (its last chunk), written at the launch sites from host
+// state only; a layer that has not run yet has a null name.
+struct FullPathRecord {
+  // Conv1: "ring_f32_pool" (row-band kernel on the fp32 image, pool1 in its epilogue), "ring_f32", "ring" (the
+  // same kernel on the polyphase bf16 image), "tiles" (implicit GEMM on the polyphase image) or "taps8" (direct
+  // 11x11/4 gathers); segs = workgroups per image of the ring forms (0 otherwise)
+  const char* conv1 = nullptr;
+  int conv1_segs = 0;
+  // Conv2-5, FC6-8: "big" (conv_bf16_big.hip, id = config), "glds" (LDS-DMA ring, id = slots) or "staged"
+  // (register-staged, id = tile variant); splitk = K slices (1: no split)
+  struct Gemm {
+    const char* kernel = nullptr;
+    int id = -1, splitk = 0;
+  } gemm[7];
+};
 
 class FullEngine {
  public:
@@ -125,6 +153,7 @@ class FullEngine {
   // [N,15,15,384], 5 conv4 window [N,15,15,384], 6 conv5 [N,13,13,256], 7 pool5 [N,9216],
   // 8 fc6 [N,4096], 9 fc7 [N,4096]. Returns the element count per image (0 for a bad i).
   size_t tap(int i, int N, void* dst, hipStream_t s) const;
+  const FullPathRecord& last_path() const { return path_; }
 
  private:
   hipEvent_t mark_ = nullptr;
@@ -139,6 +168,7 @@ class FullEngine {
   hipError_t conv(Layer& L, int N, int Hp, int Wp, const void* x, hip::OutViewB out, float* out_f32, bool relu,
                   hipStream_t s);
   Layer L_[8];
+  FullPathRecord path_;
   Knobs k_;
   int classes_, max_batch_, chunk_;
   int cus_ = 256;  // compute units (the wide-tile kernel's cost model)

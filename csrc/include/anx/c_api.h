@@ -153,6 +153,12 @@ int anx_engine_get_knob(void* engine, const char* name, int* value);
 int anx_engine_last_path(void* engine, char* buf, size_t cap);
 /* bf16 activation tap `i` of the last forward (FullEngine::tap) into dst; *elems = per-image count */
 int anx_full_tap(void* engine, int i, int N, void* dst, size_t* elems, void* stream);
+/* Which kernels the bf16 engine's last forward launched (its last chunk), recorded at the launch sites, as a JSON
+   object {"conv1": {"form": "ring_f32_pool|ring_f32|ring|tiles|taps8", "segs": workgroups per image of the ring
+   forms | null}, "conv2" .. "conv5", "fc6" .. "fc8": {"kernel": "big|glds|staged", "id": wide-tile config | LDS-DMA
+   slots | tile variant, "splitk": K slices}} (a layer that has not run yet: null) written into buf (cap bytes; 1024
+   suffice). No device call: safe between forwards and during stream capture. */
+int anx_full_last_path(void* engine, char* buf, size_t cap);
 int anx_full_set_knob(void* engine, const char* name, int value);
 int anx_full_get_knob(void* engine, const char* name, int* value);
 /* the defaults a new engine starts from (built-in values overridden by ANX_* environment variables) */

@@ -81,6 +81,35 @@ int anx_full_tap(void* e, int i, int N, void* dst, size_t* elems, void* stream) 
   *elems = static_cast<anx::FullEngine*>(e)->tap(i, N, dst, S(stream));
   return *elems ? 0 : fail("anx_full_tap: bad tap index or batch");
 }
+// The kernels the engine's last forward launched (anx::FullPathRecord) as one JSON object. Host state only.
+int anx_full_last_path(void* e, char* buf, size_t cap) {
+  return guarded("anx_full_last_path", [&] {
+    if (!e) return fail("anx_full_last_path: no engine");
+    if (!buf || cap == 0) return fail("anx_full_last_path: no buffer");
+    const anx::FullPathRecord& p = static_cast<anx::FullEngine*>(e)->last_path();
+    std::string j = "{\"conv1\": ";
+    if (p.conv1)
+      j += std::string("{\"form\": \"") + p.conv1 + "\", \"segs\": " +
+           (p.conv1_segs ? std::to_string(p.conv1_segs) : std::string("null")) + "}";
+    else
+      j += "null";
+    static const char* const names[7] = {"conv2", "conv3", "conv4", "conv5", "fc6", "fc7", "fc8"};
+    for (int i = 0; i < 7; ++i) {
+      const anx::FullPathRecord::Gemm& g = p.gemm[i];
+      j += std::string(", \"") + names[i] + "\": ";
+      if (g.kernel)
+        j += std::string("{\"kernel\": \"") + g.kernel + "\", \"id\": " + std::to_string(g.id) +
+             ", \"splitk\": " + std::to_string(g.splitk) + "}";
+      else
+        j += "null";
+    }
+    j += "}";
+    if (j.size() + 1 > cap) return fail("anx_full_last_path: buffer too small (" + std::to_string(j.size() + 1) + " bytes)");
+    j.copy(buf, j.size());
+    buf[j.size()] = 0;
+    return 0;
+  });
+}
 int anx_full_set_knob(void* e, const char* name, int value) {
   if (anx::set_knob(static_cast<anx::FullEngine*>(e)->knobs(), name, value) != 0)
     return fail(std::string("bad knob or value: ") + (name ? name : "(null)"));

@@ -151,28 +151,42 @@ hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip:
     L.key = p.variant;
   }
   const bool fc = p.Hp == 1 && p.Wp == 1 && p.F == 1;
+  // what ran (last_path): the launchers write id at their launch. Conv1 here is path_.conv1's "tiles" / "taps8".
+  FullPathRecord::Gemm scratch, &rec = &L == &L_[0] ? scratch : path_.gemm[&L - &L_[1]];
+  auto big = [&](int ksplit) {
+    rec.kernel = "big";
+    rec.splitk = ksplit;
+    return &rec.id;
+  };
+  auto tile = [&](int ksplit, hipError_t e) {  // conv2d_bf16 wrote the slot count into rec.id
+    rec.kernel = rec.id ? "glds" : "staged";
+    if (!rec.id) rec.id = p.variant;
+    rec.splitk = ksplit;
+    return e;
+  };
   if (fc && k_.bf16_big != -2) {  // wide-tile FC: one 256-row tile of the batch, K split over the CUs
     hip::BigFc f = hip::pick_bf16_big_fc(p, cus_, k_.bf16_fc_cfg, k_.bf16_fc_minkt);
     if (f.cfg >= 0 && k_.bf16_big >= 0 && hip::conv_bf16_big_ok(p, k_.bf16_big, hip::OutViewB{B(ws_), 1, 1, p.Kg, 0, 0, 0}))
       f.cfg = k_.bf16_big;
     if (f.cfg >= 0 && (f.ksplit > 1 || out_f32)) {
       ANX_TRY(hip::conv2d_bf16_big(p, f.cfg, x, L.wp, L.koff, L.bias, hip::OutViewB{B(ws_), 1, 1, p.Kg, 0, 0, 0}, relu,
-                                   s, hip::SplitK{f.ksplit, ws_}));
+                                   s, hip::SplitK{f.ksplit, ws_}, big(f.ksplit)));
       return hip::splitk_reduce_bf16(ws_, f.ksplit, N, L.K, L.bias, relu, out, out_f32, s);
     }
-    if (f.cfg >= 0) return hip::conv2d_bf16_big(p, f.cfg, x, L.wp, L.koff, L.bias, out, relu, s);
+    if (f.cfg >= 0) return hip::conv2d_bf16_big(p, f.cfg, x, L.wp, L.koff, L.bias, out, relu, s, {}, big(1));
   }
   const int ks = hip::fc_split_k(p);
   if (ks > 1) {  // FC layer at a small batch: K split over ~one workgroup per CU, then a reduce
-    ANX_TRY(hip::conv2d_bf16(p, x, L.wp, L.koff, L.bias, out, out_f32, relu, s, hip::SplitK{ks, ws_}, k_.bf16_glds));
+    ANX_TRY(tile(ks, hip::conv2d_bf16(p, x, L.wp, L.koff, L.bias, out, out_f32, relu, s, hip::SplitK{ks, ws_},
+                                      k_.bf16_glds, &rec.id)));
     return hip::splitk_reduce_bf16(ws_, ks, N, L.K, L.bias, relu, out, out_f32, s);
   }
   if (!fc && !out_f32 && k_.bf16_big != -2) {  // wide-tile kernel: forced config if it applies, else the cost model
     const int cfg = k_.bf16_big >= 0 && hip::conv_bf16_big_ok(p, k_.bf16_big, out) ? k_.bf16_big
                                                                                     : hip::pick_bf16_big_cfg(p, out, cus_);
-    if (cfg >= 0) return hip::conv2d_bf16_big(p, cfg, x, L.wp, L.koff, L.bias, out, relu, s);
+    if (cfg >= 0) return hip::conv2d_bf16_big(p, cfg, x, L.wp, L.koff, L.bias, out, relu, s, {}, big(1));
   }
-  return hip::conv2d_bf16(p, x, L.wp, L.koff, L.bias, out, out_f32, relu, s, {}, k_.bf16_glds);
+  return tile(1, hip::conv2d_bf16(p, x, L.wp, L.koff, L.bias, out, out_f32, relu, s, {}, k_.bf16_glds, &rec.id));
 }
 
 hipError_t FullEngine::forward(const float* x, int N, float* logits, hipStream_t s, bool mark) {
@@ -186,19 +200,31 @@ hipError_t FullEngine::forward(const float* x, int N, float* logits, hipStream_t
     if (poly1_) {
       if (k_.bf16_conv1 == 2) {  // the fp32 image straight into the row-band kernel (no polyphase copy)
         const OutViewB q2v{B(q2_), 31, 31, 96, 2, 2, 0};
+        hip::RingRan ran;
         ANX_TRY(hip::conv1_bf16_ring(xn, n, w1ring_, L_[0].bias, OutViewB{B(c1_), 55, 55, 96, 0, 0, 0}, true, s, cus_,
-                                     true, k_.bf16_pool1 ? &q2v : nullptr));
+                                     true, k_.bf16_pool1 ? &q2v : nullptr, &ran));
         pooled = k_.bf16_pool1 != 0;
+        path_.conv1 = ran.pool ? "ring_f32_pool" : "ring_f32";
+        path_.conv1_segs = ran.segs;
       } else {
         ANX_TRY(hip::f32_to_bf16_s2d4(xn, xb_, n, 227, 227, s));
-        if (k_.bf16_conv1 == 1)
-          ANX_TRY(hip::conv1_bf16_ring(xb_, n, w1ring_, L_[0].bias, OutViewB{B(c1_), 55, 55, 96, 0, 0, 0}, true, s, cus_));
-        else
+        if (k_.bf16_conv1 == 1) {
+          hip::RingRan ran;
+          ANX_TRY(hip::conv1_bf16_ring(xb_, n, w1ring_, L_[0].bias, OutViewB{B(c1_), 55, 55, 96, 0, 0, 0}, true, s, cus_,
+                                       false, nullptr, &ran));
+          path_.conv1 = "ring";
+          path_.conv1_segs = ran.segs;
+        } else {
           ANX_TRY(conv(L_[0], n, 57, 57, xb_, OutViewB{B(c1_), 55, 55, 96, 0, 0, 0}, nullptr, true, s));
+          path_.conv1 = "tiles";
+          path_.conv1_segs = 0;
+        }
       }
     } else {
       ANX_TRY(hip::f32_to_bf16(xn, xb_, static_cast<size_t>(n) * 227 * 227 * 3, s));
       ANX_TRY(conv(L_[0], n, 227, 227, xb_, OutViewB{B(c1_), 55, 55, 96, 0, 0, 0}, nullptr, true, s));
+      path_.conv1 = "taps8";
+      path_.conv1_segs = 0;
     }
     if (!pooled) ANX_TRY(hip::maxpool_bf16(c1_, n, 55, 55, 96, 3, 2, OutViewB{B(q2_), 31, 31, 96, 2, 2, 0}, s));
     ANX_TRY(conv(L_[1], n, 31, 31, q2_, OutViewB{B(c2_), 27, 27, 256, 0, 0, 0}, nullptr, true, s));

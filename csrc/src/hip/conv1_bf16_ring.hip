@@ -432,7 +432,7 @@ void pack_conv1_ring_weights(const float* w_k48_33, std::vector<uint16_t>& out) 
 size_t conv1_ring_weight_bytes() { return kWBytes; }
 
 hipError_t conv1_bf16_ring(const void* xin, int N, const void* wpacked, const float* bias, OutViewB out, bool relu,
-                           hipStream_t s, int cus, bool f32_input, const OutViewB* pool_out) {
+                           hipStream_t s, int cus, bool f32_input, const OutViewB* pool_out, RingRan* ran) {
   if (N <= 0) return hipSuccess;
   if (!relu || !out.base || out.Cb % 4 || out.c_off % 4 || static_cast<long>(N) * kP * kRowB >= (1L << 31) ||
       static_cast<long>(N) * out.Hb * out.Wb * out.Cb * 2 >= (1L << 31) || out.Hb < kHo + out.h_off ||
@@ -489,6 +489,7 @@ hipError_t conv1_bf16_ring(const void* xin, int N, const void* wpacked, const fl
     if (!dbg && hipMalloc(&dbg, 64 * 8 * 8) != hipSuccess) return hipErrorOutOfMemory;
     a.dbg = dbg;
   }
+  if (ran) *ran = RingRan{a.segs, a.pool != 0};
   if (f32_input)
     conv1_bf16_ring_kernel<true><<<static_cast<unsigned>(N * a.segs), kNT, a.pool ? kLdsPool : kLds, s>>>(a);
   else

@@ -665,7 +665,8 @@ uint16_t f32_to_bf16_bits(float f) {  // round to nearest even, NaN kept NaN
 }
 
 hipError_t conv2d_bf16(const ConvPlanB& p, const void* x, const void* wpacked, const int* koff, const float* bias,
-                       OutViewB out, float* out_f32, bool relu, hipStream_t s, SplitK split, int glds) {
+                       OutViewB out, float* out_f32, bool relu, hipStream_t s, SplitK split, int glds,
+                       int* ran_slots) {
   const long M = static_cast<long>(p.N) * p.Ho * p.Wo;
   if (M == 0) return hipSuccess;
   if (static_cast<long>(p.N) * p.Hp * p.Wp * p.C >= (1L << 31)) return hipErrorInvalidValue;
@@ -745,6 +746,7 @@ hipError_t conv2d_bf16(const ConvPlanB& p, const void* x, const void* wpacked, c
         conv_bf16_glds_kernel<3, 2, float><<<grid, kThreads, lds_r, s>>>(a);
       else
         conv_bf16_glds_kernel<3, 2, bf16><<<grid, kThreads, lds_r, s>>>(a);
+      if (ran_slots) *ran_slots = nst;
       return hipGetLastError();
     }
   }
@@ -758,6 +760,7 @@ hipError_t conv2d_bf16(const ConvPlanB& p, const void* x, const void* wpacked, c
     default: return hipErrorInvalidValue;
   }
 #undef ANX_LAUNCH
+  if (ran_slots) *ran_slots = 0;
   return hipGetLastError();
 }
 

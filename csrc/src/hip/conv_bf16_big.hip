@@ -572,7 +572,7 @@ BigFc pick_bf16_big_fc(const ConvPlanB& p, int cus, int cfg, int min_kt) {
 }
 
 hipError_t conv2d_bf16_big(const ConvPlanB& p, int cfg, const void* x, const void* wpacked, const int* koff,
-                           const float* bias, OutViewB out, bool relu, hipStream_t s, SplitK split) {
+                           const float* bias, OutViewB out, bool relu, hipStream_t s, SplitK split, int* ran_cfg) {
   if (!conv_bf16_big_ok(p, cfg, out)) return hipErrorInvalidValue;
   const int ksplit = std::max(1, split.ksplit);
   const bool slab = split.ws != nullptr;  // fp32 slabs (also at ksplit 1: an fp32 result via the reduce)
@@ -581,6 +581,7 @@ hipError_t conv2d_bf16_big(const ConvPlanB& p, int cfg, const void* x, const voi
   const long M = static_cast<long>(p.N) * p.Ho * p.Wo;
   if (M == 0) return hipSuccess;
   const BigCfg c = kCfg[cfg];
+  if (ran_cfg) *ran_cfg = cfg;
   ArgsW a{};
   a.x = static_cast<const bf16*>(x);
   a.w = static_cast<const bf16*>(wpacked);

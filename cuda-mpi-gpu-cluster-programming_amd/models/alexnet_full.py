@@ -223,6 +223,20 @@ class AlexNetFull:
         nat.call("anx_full_tap", self._h, i, N, y.data_ptr(), C.byref(n), nat.stream_ptr(self.device))
         return y
 
+    def last_path(self, lane: int = 0) -> dict:
+        """Which kernels the last forward of this model's engine launched (``lane`` > 0: that side lane's
+        engine; of a chunked forward, the last chunk): ``{"conv1": {"form": "ring_f32_pool" | "ring_f32" |
+        "ring" | "tiles" | "taps8", "segs": workgroups per image of the ring forms or None}, "conv2" ..
+        "conv5", "fc6" .. "fc8": {"kernel": "big" | "glds" | "staged", "id": wide-tile config | LDS-DMA
+        slots | tile variant, "splitk": K slices}}``, ``None`` for a layer that has not run. The engine
+        records it where it launches, and reading it makes no device call."""
+        if lane:
+            return self._lanes[lane - 1].last_path()
+        import json
+        buf = C.create_string_buffer(1024)
+        nat.call("anx_full_last_path", self._h, buf, len(buf))
+        return json.loads(buf.value.decode())
+
 
 def reference_forward(x: torch.Tensor, w: dict, groups2: int = 1, lrn_mode: str = "div_n",
                       dtype=torch.float32) -> torch.Tensor:

@@ -78,8 +78,10 @@ def test_s2d4_polyphase_input_exact(cuda):
 @pytest.mark.parametrize("groups2", [1, 2])
 def test_full_alexnet_per_layer_vs_bf16_oracle(cuda, groups2):
     """Each layer of the engine, fed the engine's own (bf16) input of that layer, against the same
-    layer in fp64 on bf16-rounded operands, rounded to bf16: only the fp32 summation order differs,
-    so every layer agrees to <= 1e-2 of its max (|one bf16 ulp| = 0.4 %) and <= 4e-3 in L2."""
+    layer in fp64 on bf16-rounded operands and the fp32 bias the engine keeps, rounded to bf16: only
+    the fp32 summation order differs, so every layer agrees to <= 1e-2 of its max (|one bf16 ulp| =
+    0.4 %) and <= 4e-3 in L2; the pools are exact. (The per-element bound, with nonzero biases, is
+    test_full_alexnet_oracle_gpu.py's.)"""
     N = 6
     m = AlexNetFull(seed=9, device=cuda, max_batch=N, groups2=groups2, knobs={"bf16_pool1": 0})  # conv1 map in tap 0
     x = (init_input(N, "rand", seed=9) * 10).to(cuda)
@@ -90,7 +92,7 @@ def test_full_alexnet_per_layer_vs_bf16_oracle(cuda, groups2):
     nhwc = lambda t: t.permute(0, 2, 3, 1)  # noqa: E731
 
     def conv(h, name, stride=1, pad=0, groups=1, relu=True):
-        y = F.conv2d(nchw(h), _q(w["w_" + name]), _q(w["b_" + name]), stride=stride, padding=pad, groups=groups)
+        y = F.conv2d(nchw(h), _q(w["w_" + name]), w["b_" + name].double(), stride=stride, padding=pad, groups=groups)
         return nhwc(F.relu(y) if relu else y)
 
     def check(got, ref, what):
@@ -100,16 +102,16 @@ def test_full_alexnet_per_layer_vs_bf16_oracle(cuda, groups2):
 
     pool = lambda h: nhwc(F.max_pool2d(nchw(h), 3, 2))  # noqa: E731
     check(taps[0], _q(conv(_q(x), "conv1", stride=4)), "conv1")
-    check(taps[1][:, 2:-2, 2:-2], pool(taps[0]), "pool1")
+    assert torch.equal(taps[1][:, 2:-2, 2:-2], pool(taps[0])), "pool1"
     check(taps[2], _q(conv(taps[1], "conv2", groups=groups2)), "conv2")
     lrn = nhwc(F.local_response_norm(nchw(pool(taps[2])), 5, alpha=1e-4, beta=0.75, k=2.0))
     check(taps[3][:, 1:-1, 1:-1], _q(lrn), "pool2+lrn")
     check(taps[4][:, 1:-1, 1:-1], _q(conv(taps[3], "conv3")), "conv3")
     check(taps[5][:, 1:-1, 1:-1], _q(conv(taps[4], "conv4")), "conv4")
     check(taps[6], _q(conv(taps[5], "conv5")), "conv5")
-    check(taps[7], pool(taps[6]).reshape(N, -1), "pool5")
+    assert torch.equal(taps[7], pool(taps[6]).reshape(N, -1)), "pool5"
     fc = lambda h, k, relu=True: (F.relu if relu else (lambda t: t))(  # noqa: E731
-        h @ _q(w["w_" + k]).T + _q(w["b_" + k]))
+        h @ _q(w["w_" + k]).T + w["b_" + k].double())
     check(taps[8], _q(fc(taps[7], "fc6")), "fc6")
     check(taps[9], _q(fc(taps[8], "fc7")), "fc7")
     check(logits, fc(taps[9], "fc8", relu=False), "fc8")
@@ -136,7 +138,8 @@ def test_bf16_wide_tile_kernel_matches_register_staged(cuda, cfg):
     """The wide-tile kernel (conv_bf16_big.hip; -1 = the cost model's per-layer pick, else that
     config forced wherever it fits) sums each output's products in the register-staged kernel's
     order: conv1..pool5 activations bit-identical. FC6-8 run K split another number of ways, so
-    they agree to summation order only."""
+    they agree to summation order only. last_path() shows that the forced config ran (every config
+    of the list fits Conv2-5 of this network; where none fitted the cost model's pick would run)."""
     N = 37  # partial M tiles everywhere
     x = (init_input(N, "rand", seed=12) * 10).to(cuda)
     ref_m = AlexNetFull(seed=12, device=cuda, max_batch=N, knobs={"bf16_glds": 0, "bf16_big": -2})
@@ -144,6 +147,13 @@ def test_bf16_wide_tile_kernel_matches_register_staged(cuda, cfg):
     ref_taps = [ref_m.tap(i, N) for i in range(10)]
     m = AlexNetFull(seed=12, device=cuda, max_batch=N, knobs={"bf16_big": cfg})
     got = m(x).double()
+    path = m.last_path()
+    ran = {name: (v["kernel"], v["id"]) for name, v in path.items() if name != "conv1"}
+    assert "big" not in {v["kernel"] for name, v in ref_m.last_path().items() if name != "conv1"}
+    if cfg >= 0:
+        assert [n for n in ("conv2", "conv3", "conv4", "conv5") if ran[n] == ("big", cfg)], (cfg, path)
+    else:
+        assert all(ran[n][0] == "big" for n in ("conv2", "conv3", "conv4", "conv5")), path
     for i in range(8):
         assert torch.equal(m.tap(i, N), ref_taps[i]), i
     for i in (8, 9):
