@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "anx/knobs.hpp"
+#include "anx/ops.hpp"
 #include "anx/shapes.hpp"
 
 namespace anx {
@@ -103,6 +104,12 @@ struct RingRan {
 hipError_t conv1_bf16_ring(const void* x, int N, const void* wpacked, const float* bias, OutViewB out, bool relu,
                            hipStream_t s, int cus = 256, bool f32_input = false, const OutViewB* pool_out = nullptr,
                            RingRan* ran = nullptr);
+// The fp32-image form reading the byte image [N,227,227,3] instead (nm.C == 3; x may start at any byte address):
+// the loader decodes with fmaf(float(b), nm.sc[c], nm.of[c]) in registers, no float copy of the input exists.
+// Same pool_out / ran contract and the same bits as decode_u8 + conv1_bf16_ring(f32_input = true).
+hipError_t conv1_bf16_ring_u8(const uint8_t* x, const U8Norm& nm, int N, const void* wpacked, const float* bias,
+                              OutViewB out, bool relu, hipStream_t s, int cus = 256, const OutViewB* pool_out = nullptr,
+                              RingRan* ran = nullptr);
 
 }  // namespace hip
 
@@ -120,7 +127,9 @@ void full_weight_shapes(int classes, int groups2, size_t wn[8], size_t bn[8]);
 struct FullPathRecord {
   // Conv1: "ring_f32_pool" (row-band kernel on the fp32 image, pool1 in its epilogue), "ring_f32", "ring" (the
   // same kernel on the polyphase bf16 image), "tiles" (implicit GEMM on the polyphase image) or "taps8" (direct
-  // 11x11/4 gathers); segs = workgroups per image of the ring forms (0 otherwise)
+  // 11x11/4 gathers); segs = workgroups per image of the ring forms (0 otherwise). A byte forward whose ring kernel
+  // loaded the bytes itself (last_input "u8_ring") reports "ring_u8_pool" / "ring_u8"; one that decoded first
+  // ("u8_decode") reports the float form that then ran.
   const char* conv1 = nullptr;
   int conv1_segs = 0;
   // Conv2-5, FC6-8: "big" (conv_bf16_big.hip, id = config), "glds" (LDS-DMA ring, id = slots) or "staged"
@@ -140,6 +149,18 @@ class FullEngine {
   FullEngine& operator=(const FullEngine&) = delete;
   // x: [N,227,227,3] fp32 device; logits: [N,classes] fp32 device.
   hipError_t forward(const float* x, int N, float* logits, hipStream_t s, bool mark = false);
+  // Byte input: x [N,227,227,3] uint8 device, from any byte address. A byte b of channel c means
+  // fmaf(float(b), scale[c], offset[c]) (cpu::decode_u8; default 1/255, 0) and the logits and every tap equal
+  // those of forward() fed the decoded image, bit for bit; chunking and mark as forward(). With the row-band Conv1
+  // on the image (bf16_conv1 2) and Knobs::bf16_u8 that kernel loads the bytes ("u8_ring": no float copy of the
+  // input exists); everywhere else hip::decode_u8 writes the launch chunk as fp32 into a workspace and the float
+  // path runs unchanged ("u8_decode"). The first byte call that needs the workspace allocates it (chunk-sized,
+  // freed with the engine), never inside a stream capture: warm up once before capturing a graph.
+  hipError_t forward_u8(const uint8_t* x, int N, float* logits, hipStream_t s, bool mark = false);
+  void set_input_norm(const float* scale, const float* offset);  // three values each
+  // How the last forward's input reached Conv1: "f32", "u8_ring", "u8_decode"; null before the first. Recorded at
+  // the launch site from host state.
+  const char* last_input() const { return input_; }
   // forward(..., mark = true) records this engine's mark event on `s` once Conv2 + Pool2/LRN of the
   // first chunk are enqueued (about half of the forward): wait_mark makes another stream wait for it,
   // which staggers free-running lanes (AlexNetFull.forward_async) by half a forward.
@@ -167,6 +188,11 @@ class FullEngine {
   };
   hipError_t conv(Layer& L, int N, int Hp, int Wp, const void* x, hip::OutViewB out, float* out_f32, bool relu,
                   hipStream_t s);
+  // the one layer chain: exactly one of xf (floats) / xu (bytes) is set
+  hipError_t run(const float* xf, const uint8_t* xu, int N, float* logits, hipStream_t s, bool mark);
+  hip::U8Norm norm_{3, {1.f / 255.f, 1.f / 255.f, 1.f / 255.f}, {0.f, 0.f, 0.f}};  // byte input: scale / offset
+  float* xdec_ = nullptr;          // byte input decoded to fp32 (u8_decode), chunk_ images, allocated on first need
+  const char* input_ = nullptr;    // last_input()
   Layer L_[8];
   FullPathRecord path_;
   Knobs k_;

@@ -100,6 +100,17 @@ int anx_full_forward(void* e, const float* x, int N, float* logits, void* stream
    anx_full_wait_mark makes `stream` wait for the last recorded mark of engine e. */
 int anx_full_forward_mark(void* e, const float* x, int N, float* logits, void* stream);
 int anx_full_wait_mark(void* e, void* stream);
+/* Byte input ([N,227,227,3] uint8 on the device, from any byte address): a byte b of channel c means
+   fmaf((float)b, scale[c], offset[c]) in fp32 (default scale 1/255, offset 0; set_input_norm takes 3 values each).
+   The _u8 entry points have the contracts of their float twins and give the logits and taps of the float twin fed
+   the decoded image, bit for bit. With the row-band Conv1 on the image (knob bf16_conv1 = 2) and knob bf16_u8 = 1
+   that kernel loads the bytes itself; everywhere else the launch chunk is decoded into a workspace that the first
+   such call allocates (never inside a stream capture: warm up once before capturing). anx_full_last_input writes
+   "f32", "u8_ring" or "u8_decode" (how the last forward fed Conv1; "" before the first) into buf; no device call. */
+int anx_full_forward_u8(void* e, const uint8_t* x, int N, float* logits, void* stream);
+int anx_full_forward_mark_u8(void* e, const uint8_t* x, int N, float* logits, void* stream);
+int anx_full_set_input_norm(void* e, const float* scale, const float* offset);
+int anx_full_last_input(void* e, char* buf, size_t cap);
 
 /* ---- host engine (same contract as the device engine; V1 / V2 CPU ranks) ---- */
 int anx_cpu_engine_create(void** out, const anx_block_c* b1, const anx_block_c* b2, int H, int W, const float* w1,

@@ -43,6 +43,15 @@ struct Knobs {
                            // 1 = the same on the s2d4 polyphase copy, 0 = s2d4 + the implicit-GEMM tile kernels
   int bf16_pool1 = 1;      // bf16 pool1: 1 = in the Conv1 ring kernel's epilogue (bf16_conv1 2, one workgroup per
                            // image: the 55x55 map never reaches HBM), 0 = Conv1 writes it and maxpool_bf16 reads it
+  int bf16_u8 = 1;         // bf16 byte input (FullEngine::forward_u8) where the row-band Conv1 reads the image (bf16_conv1
+                           // 2): 1 = that kernel loads the bytes itself and decodes them in registers (no float copy
+                           // of the input on the device), 0 = the decode kernel into a workspace, then the float
+                           // kernel. Same bits either way; every other Conv1 form always decodes first.
+                           // Default 1 by measurement: 256 device-resident images, one lane, step median 0.652 ms
+                           // (1) vs 0.714 ms (0), float input 0.655 ms (a second run: 0.642 / 0.717 / 0.689); the
+                           // byte kernel alone 89.6 us against 59.3 us of decode + 88.2 us of the float kernel behind
+                           // it (100.7 us on floats that no decode just wrote); host-fed 1.35 ms as bytes vs 3.48 ms
+                           // as floats (profiles/bf16_u8_input/)
   int conv1_occ = 0;       // cap on the Conv1 Winograd GEMM's workgroups per CU (LDS padding; 0 = none: 4)
   int conv2_occ = -1;      // ... and Conv2's (0 = none: 2; -1 = auto: 1 when the launch has <= one workgroup per
                            // CU); a cap leaves room for a concurrent lane's kernels
@@ -96,7 +105,7 @@ struct Knobs {
 };
 
 // Built-in defaults, overridden by ANX_CONV1_ALGO, ANX_CONV2_ALGO, ANX_CHUNK1, ANX_CHUNK2,
-// ANX_BF16_GLDS, ANX_BF16_BIG, ANX_CONV1_OCC, ANX_CONV2_OCC, ANX_CONV1_BAND, ANX_FUSE_POOL1,
+// ANX_BF16_GLDS, ANX_BF16_BIG, ANX_BF16_U8, ANX_CONV1_OCC, ANX_CONV2_OCC, ANX_CONV1_BAND, ANX_FUSE_POOL1,
 // ANX_CONV1_SUB, ANX_CONV2_SUB, ANX_CONV1_U8, ANX_CONV1_FUSED, ANX_CONV1_POOL, ANX_CONV2_POOL, ANX_CONV2_TILE,
 // ANX_CONV2_SCHED, ANX_LRN_WGS when set.
 Knobs default_knobs();

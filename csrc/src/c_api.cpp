@@ -118,7 +118,10 @@ anx::hip::ConvPlan plan_from_ints(const int* o) {
 extern "C" {
 
 const char* anx_last_error(void) { return g_err.c_str(); }
-int anx_abi_version(void) { return 2; }  // 2: byte input (anx_*_u8, anx_*_set_input_norm, anx_engine_last_input)
+// 2: byte input (anx_*_u8, anx_*_set_input_norm, anx_engine_last_input)
+// 3: byte input of the bf16 full model (anx_full_forward_u8, anx_full_forward_mark_u8, anx_full_set_input_norm,
+//    anx_full_last_input; knob bf16_u8)
+int anx_abi_version(void) { return 3; }
 
 int anx_device_count(void) {
   int n = 0;

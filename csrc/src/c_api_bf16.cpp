@@ -71,6 +71,45 @@ int anx_full_forward_mark(void* e, const float* x, int N, float* logits, void* s
   });
 }
 
+int anx_full_forward_u8(void* e, const uint8_t* x, int N, float* logits, void* stream) {
+  return guarded("anx_full_forward_u8", [&] {
+    if (!e) return fail("anx_full_forward_u8: no engine");
+    if (N > 0 && (!x || !logits)) return fail("anx_full_forward_u8: no buffer");
+    return hip_status(static_cast<anx::FullEngine*>(e)->forward_u8(x, N, logits, S(stream)), "full forward (bytes)");
+  });
+}
+
+int anx_full_forward_mark_u8(void* e, const uint8_t* x, int N, float* logits, void* stream) {
+  return guarded("anx_full_forward_mark_u8", [&] {
+    if (!e) return fail("anx_full_forward_mark_u8: no engine");
+    if (N > 0 && (!x || !logits)) return fail("anx_full_forward_mark_u8: no buffer");
+    return hip_status(static_cast<anx::FullEngine*>(e)->forward_u8(x, N, logits, S(stream), true), "full forward (bytes)");
+  });
+}
+
+int anx_full_set_input_norm(void* e, const float* scale, const float* offset) {
+  return guarded("anx_full_set_input_norm", [&] {
+    if (!e) return fail("anx_full_set_input_norm: no engine");
+    if (!scale || !offset) return fail("anx_full_set_input_norm: 3 scale and 3 offset values");
+    static_cast<anx::FullEngine*>(e)->set_input_norm(scale, offset);
+    return 0;
+  });
+}
+
+// How the last forward's input reached Conv1 ("" before the first). Host state only.
+int anx_full_last_input(void* e, char* buf, size_t cap) {
+  return guarded("anx_full_last_input", [&] {
+    if (!e) return fail("anx_full_last_input: no engine");
+    if (!buf || cap == 0) return fail("anx_full_last_input: no buffer");
+    const char* v = static_cast<anx::FullEngine*>(e)->last_input();
+    const std::string j = v ? v : "";
+    if (j.size() + 1 > cap) return fail("anx_full_last_input: buffer too small");
+    j.copy(buf, j.size());
+    buf[j.size()] = 0;
+    return 0;
+  });
+}
+
 int anx_full_wait_mark(void* e, void* stream) {
   return guarded("anx_full_wait_mark", [&] {
     return hip_status(static_cast<anx::FullEngine*>(e)->wait_mark(S(stream)), "full wait mark");

@@ -130,7 +130,8 @@ FullEngine::~FullEngine() {
   for (Layer& L : L_)
     for (void* p : {L.wp, static_cast<void*>(L.koff), static_cast<void*>(L.bias)})
       if (p) (void)hipFree(p);
-  for (void* p : {xb_, c1_, q2_, c2_, q3_, q4_, q5_, c5_, f6_, f7_, f8_, static_cast<void*>(ws_), w1ring_})
+  for (void* p : {xb_, c1_, q2_, c2_, q3_, q4_, q5_, c5_, f6_, f7_, f8_, static_cast<void*>(ws_), w1ring_,
+                  static_cast<void*>(xdec_)})
     if (p) (void)hipFree(p);
 }
 
@@ -190,21 +191,50 @@ hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip:
 }
 
 hipError_t FullEngine::forward(const float* x, int N, float* logits, hipStream_t s, bool mark) {
+  return run(x, nullptr, N, logits, s, mark);
+}
+
+hipError_t FullEngine::forward_u8(const uint8_t* x, int N, float* logits, hipStream_t s, bool mark) {
+  return run(nullptr, x, N, logits, s, mark);
+}
+
+void FullEngine::set_input_norm(const float* scale, const float* offset) {
+  for (int c = 0; c < 3; ++c) norm_.sc[c] = scale[c], norm_.of[c] = offset[c];
+}
+
+hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* logits, hipStream_t s, bool mark) {
   if (mark && !mark_) ANX_TRY(hipEventCreateWithFlags(&mark_, hipEventDisableTiming));
   using hip::OutViewB;
   auto B = [](void* p) { return static_cast<__bf16*>(p); };
+  constexpr size_t kImage = 227 * 227 * 3;
+  // bytes straight into the row-band kernel, else decoded into the workspace first
+  const bool u8_ring = xu && poly1_ && k_.bf16_conv1 == 2 && k_.bf16_u8 != 0;
+  if (xu && !u8_ring && !xdec_) {
+    // one launch chunk, once; a captured stream must not see the allocation
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
+      return hipErrorStreamCaptureUnsupported;
+    ANX_TRY(hipMalloc(reinterpret_cast<void**>(&xdec_), static_cast<size_t>(chunk_) * kImage * sizeof(float)));
+  }
   for (int n0 = 0; n0 < N; n0 += chunk_) {
     const int n = std::min(chunk_, N - n0);
-    const float* xn = x + static_cast<size_t>(n0) * 227 * 227 * 3;
+    const float* xn = xf ? xf + static_cast<size_t>(n0) * kImage : xdec_;
+    if (xu && !u8_ring) ANX_TRY(hip::decode_u8(xu + static_cast<size_t>(n0) * kImage, xdec_, n * kImage, norm_, s));
+    input_ = !xu ? "f32" : u8_ring ? "u8_ring" : "u8_decode";
     bool pooled = false;  // pool1 done with Conv1
     if (poly1_) {
-      if (k_.bf16_conv1 == 2) {  // the fp32 image straight into the row-band kernel (no polyphase copy)
+      if (k_.bf16_conv1 == 2) {  // the image straight into the row-band kernel (no polyphase copy)
         const OutViewB q2v{B(q2_), 31, 31, 96, 2, 2, 0};
+        const OutViewB c1v{B(c1_), 55, 55, 96, 0, 0, 0};
         hip::RingRan ran;
-        ANX_TRY(hip::conv1_bf16_ring(xn, n, w1ring_, L_[0].bias, OutViewB{B(c1_), 55, 55, 96, 0, 0, 0}, true, s, cus_,
-                                     true, k_.bf16_pool1 ? &q2v : nullptr, &ran));
+        if (u8_ring)
+          ANX_TRY(hip::conv1_bf16_ring_u8(xu + static_cast<size_t>(n0) * kImage, norm_, n, w1ring_, L_[0].bias, c1v, true,
+                                          s, cus_, k_.bf16_pool1 ? &q2v : nullptr, &ran));
+        else
+          ANX_TRY(hip::conv1_bf16_ring(xn, n, w1ring_, L_[0].bias, c1v, true, s, cus_, true,
+                                       k_.bf16_pool1 ? &q2v : nullptr, &ran));
         pooled = k_.bf16_pool1 != 0;
-        path_.conv1 = ran.pool ? "ring_f32_pool" : "ring_f32";
+        path_.conv1 = u8_ring ? (ran.pool ? "ring_u8_pool" : "ring_u8") : (ran.pool ? "ring_f32_pool" : "ring_f32");
         path_.conv1_segs = ran.segs;
       } else {
         ANX_TRY(hip::f32_to_bf16_s2d4(xn, xb_, n, 227, 227, s));

@@ -25,6 +25,20 @@
 //     fused (one workgroup per image) through LDS into the pooled map.
 // Fragments are read two K steps ahead of their MFMAs (registers triple-buffered).
 //
+// Three input forms (InKind): the polyphase bf16 copy (rows by LDS-DMA), the fp32 image and the byte image
+// (space-to-depth and conversion in the kernel: rows loaded to registers one tile ahead, written to the ring
+// converted). The byte form differs from the fp32 form only in its loader: a lane's 12 floats become 12 bytes
+// at the same offset counted in bytes, kept as three raw dwords (kRT x 3 registers in flight instead of
+// kRT x 12), decoded with fmaf(float(b), scale[c], offset[c]) (cpu::decode_u8) right before the fp32 form's
+// own packed conversion, so the ring holds the bits decode_u8 + the fp32 form would have put there. Image
+// rows are 681 bytes and a byte tensor slice starts anywhere, so these dword loads have no alignment at all:
+// they are byte-aligned buffer loads, relying on the unaligned access mode the fp32 form's 4-B-aligned 16-B
+// loads already rely on. The alternative, aligned dwords plus a per-lane funnel shift, needs a fourth dword
+// per row and its first / last dword reaches up to 3 bytes outside the tensor, where only the range check of a
+// descriptor that no longer starts at the tensor keeps it harmless; the unaligned loads touch exactly the
+// image's bytes (num_records is the exact byte count, column 56's last load is shifted back to end at the
+// row's last byte).
+//
 // Reference op: convKernel (final_project/v3_cuda_only/src/layers_cuda.cu:20-46); the full-network
 // tail is the extension's own.
 #include <hip/hip_runtime.h>
@@ -77,8 +91,10 @@ static_assert(kRT * kPieces % kWaves == 0, "a tile's row DMAs split evenly over 
 [[maybe_unused]] constexpr int kDPW = kRT * kPieces / kWaves;            // row DMAs per wave per tile (6)
 constexpr int kSPW = kPB * 12;                          // output stores per wave per tile (24)
 
+enum class InKind : int { Poly = 0, F32 = 1, U8 = 2 };
+
 struct Args {
-  const void* x;      // F32IN: [N][227][227][3] fp32 images; else [N][57][57][48] bf16 polyphase
+  const void* x;      // F32 / U8: [N][227][227][3] fp32 / byte images; Poly: [N][57][57][48] bf16 polyphase
   const bf16* w;      // [96][440] (K = tap * 48 + channel, zero past 432), kWBytes bytes
   const float* bias;  // [96]
   bf16* out;          // NHWC through the view
@@ -89,6 +105,7 @@ struct Args {
   bf16* pout;
   int pHb, pWb, pCb, ph_off, pw_off, pc_off;
   unsigned long long* dbg;  // ANX_RING_PHASES: per-workgroup phase clocks (wave 0), else null
+  float sc[3], of[3];       // U8: a byte b of channel c decodes to fmaf(float(b), sc[c], of[c])
 };
 
 // bf16(relu(acc[4j .. 4j+3] + bias)): the add as two packed f32 adds, then one packed conversion, then
@@ -115,8 +132,10 @@ __device__ __forceinline__ void sfor(F&& f) {
 // registers one tile ahead and written into the ring converted and swizzled), so neither the
 // s2d4 kernel nor its 80 MB polyphase copy runs.
 static_assert(kWaves == 4, "F32IN: wave w loads the image rows of phase w");
-template <bool F32IN>
+template <InKind IN>
 __global__ void __launch_bounds__(kNT, 1) conv1_bf16_ring_kernel(Args a) {
+  constexpr bool F32IN = IN != InKind::Poly;  // the image itself (floats or bytes): rows through registers
+  constexpr bool U8 = IN == InKind::U8;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -151,7 +170,11 @@ __global__ void __launch_bounds__(kNT, 1) conv1_bf16_ring_kernel(Args a) {
   // of column c, written as three 8-B pieces at their swizzled 16-B units. The 12 floats are three
   // 16-B loads at 4-B alignment (HSA runs buffer accesses in unaligned mode); column 56 has 9 floats
   // and its third load takes the row's last 16 B (floats 5..8), so no load reaches past the tensor.
-  [[maybe_unused]] f32x4 xw[kRT][3];
+  // U8: the same plan in bytes. Lane c's 12 bytes at byte offset (n*227 + row)*681 + 12 c are three dword loads
+  // at +0, +4, +8 (any alignment); column 56 has 9 bytes and its third load sits at +5, the row's last 4 bytes
+  // (bytes 5..8: byte 8 is that dword's top byte).
+  using xw_t = std::conditional_t<U8, unsigned, f32x4>;
+  [[maybe_unused]] xw_t xw[kRT][3];
   [[maybe_unused]] auto row_of = [&](int row0, int jj, int& row, bool& ok) {
     const int pr = row0 + jj;
     row = 4 * pr + wave;
@@ -165,10 +188,17 @@ __global__ void __launch_bounds__(kNT, 1) conv1_bf16_ring_kernel(Args a) {
       int row;
       bool ok;
       row_of(row0, jj, row, ok);
-      const int b = ok && c < kP ? ((n * 227 + row) * 681 + 12 * c) * 4 : kOOB;
-      xw[jj][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, b, 0, 0));
-      xw[jj][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, b, 16, 0));
-      xw[jj][2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, b + (c == kP - 1 ? 20 : 32), 0, 0));
+      if constexpr (U8) {
+        const int b = ok && c < kP ? (n * 227 + row) * 681 + 12 * c : kOOB;
+        xw[jj][0] = __builtin_amdgcn_raw_buffer_load_b32(xr, b, 0, 0);
+        xw[jj][1] = __builtin_amdgcn_raw_buffer_load_b32(xr, b, 4, 0);
+        xw[jj][2] = __builtin_amdgcn_raw_buffer_load_b32(xr, b + (c == kP - 1 ? 5 : 8), 0, 0);
+      } else {
+        const int b = ok && c < kP ? ((n * 227 + row) * 681 + 12 * c) * 4 : kOOB;
+        xw[jj][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, b, 0, 0));
+        xw[jj][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, b, 16, 0));
+        xw[jj][2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, b + (c == kP - 1 ? 20 : 32), 0, 0));
+      }
     }
 #endif
   };
@@ -181,9 +211,19 @@ __global__ void __launch_bounds__(kNT, 1) conv1_bf16_ring_kernel(Args a) {
       bool ok;
       row_of(row0, jj, row, ok);
       float u[12];
+      if constexpr (U8) {
+        // unpack, then the decode of cpu::decode_u8: the lane's channel pattern is fixed (f % 3)
+        float bt[12];
 #pragma unroll
-      for (int f = 0; f < 12; ++f) u[f] = xw[jj][f >> 2][f & 3];
-      u[8] = c == kP - 1 ? xw[jj][2][3] : u[8];
+        for (int f = 0; f < 12; ++f) bt[f] = static_cast<float>((xw[jj][f >> 2] >> (8 * (f & 3))) & 0xffu);
+        bt[8] = c == kP - 1 ? static_cast<float>(xw[jj][2] >> 24) : bt[8];
+#pragma unroll
+        for (int f = 0; f < 12; ++f) u[f] = __builtin_fmaf(bt[f], a.sc[f % 3], a.of[f % 3]);
+      } else {
+#pragma unroll
+        for (int f = 0; f < 12; ++f) u[f] = xw[jj][f >> 2][f & 3];
+        u[8] = c == kP - 1 ? xw[jj][2][3] : u[8];
+      }
 #pragma unroll
       for (int f = 0; f < 12; ++f) u[f] = ok && !(c == kP - 1 && f >= 9) ? u[f] : 0.f;  // column 227 / past the image
       char* col = lds + ((row0 + jj) % kSlots) * kSlotB + c * (kCh * 2);
@@ -431,16 +471,20 @@ void pack_conv1_ring_weights(const float* w_k48_33, std::vector<uint16_t>& out) 
 
 size_t conv1_ring_weight_bytes() { return kWBytes; }
 
-hipError_t conv1_bf16_ring(const void* xin, int N, const void* wpacked, const float* bias, OutViewB out, bool relu,
-                           hipStream_t s, int cus, bool f32_input, const OutViewB* pool_out, RingRan* ran) {
+namespace {
+// nm != nullptr: kind is U8 and xin a byte image decoded with *nm
+hipError_t launch_ring(const void* xin, InKind kind, const U8Norm* nm, int N, const void* wpacked, const float* bias,
+                       OutViewB out, bool relu, hipStream_t s, int cus, const OutViewB* pool_out, RingRan* ran) {
+  const bool f32_input = kind != InKind::Poly;  // the image itself, floats or bytes
   if (N <= 0) return hipSuccess;
   if (!relu || !out.base || out.Cb % 4 || out.c_off % 4 || static_cast<long>(N) * kP * kRowB >= (1L << 31) ||
       static_cast<long>(N) * out.Hb * out.Wb * out.Cb * 2 >= (1L << 31) || out.Hb < kHo + out.h_off ||
       out.Wb < kWo + out.w_off || out.Cb < kK + out.c_off)
     return hipErrorInvalidValue;
   static const hipError_t attr = [] {
-    for (const void* k : {reinterpret_cast<const void*>(conv1_bf16_ring_kernel<false>),
-                          reinterpret_cast<const void*>(conv1_bf16_ring_kernel<true>)}) {
+    for (const void* k : {reinterpret_cast<const void*>(conv1_bf16_ring_kernel<InKind::Poly>),
+                          reinterpret_cast<const void*>(conv1_bf16_ring_kernel<InKind::F32>),
+                          reinterpret_cast<const void*>(conv1_bf16_ring_kernel<InKind::U8>)}) {
       const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e != hipSuccess) return e;
     }
@@ -449,7 +493,11 @@ hipError_t conv1_bf16_ring(const void* xin, int N, const void* wpacked, const fl
   if (attr != hipSuccess) return attr;
   Args a{};
   a.x = xin;
-  if (f32_input && (reinterpret_cast<uintptr_t>(xin) & 3)) return hipErrorInvalidValue;
+  if (kind == InKind::F32 && (reinterpret_cast<uintptr_t>(xin) & 3)) return hipErrorInvalidValue;  // bytes: any address
+  if (kind == InKind::U8) {
+    if (!nm || nm->C != 3) return hipErrorInvalidValue;
+    for (int c = 0; c < 3; ++c) a.sc[c] = nm->sc[c], a.of[c] = nm->of[c];
+  }
   a.w = static_cast<const bf16*>(wpacked);
   a.bias = bias;
   a.out = out.base;
@@ -463,7 +511,10 @@ hipError_t conv1_bf16_ring(const void* xin, int N, const void* wpacked, const fl
   // one image per workgroup when the batch fills the CUs; else each image's 14 tiles split over
   // segments (each re-stages its first rows)
   a.segs = std::max(1, std::min(kTilesPerImage / 2, (std::max(1, cus) + N - 1) / N));
-  const long xb = f32_input ? static_cast<long>(N) * 227 * 227 * 3 * 4 : static_cast<long>(N) * kP * kRowB;
+  // the image, not a byte more: the range check is what turns a lane past it into zeros
+  const long xb = kind == InKind::U8    ? static_cast<long>(N) * 227 * 227 * 3
+                  : kind == InKind::F32 ? static_cast<long>(N) * 227 * 227 * 3 * 4
+                                        : static_cast<long>(N) * kP * kRowB;
   if (xb >= (1L << 31)) return hipErrorInvalidValue;
   a.xbytes = static_cast<int>(xb);
   a.obytes = static_cast<int>(static_cast<long>(N) * out.Hb * out.Wb * out.Cb * 2);
@@ -490,10 +541,12 @@ hipError_t conv1_bf16_ring(const void* xin, int N, const void* wpacked, const fl
     a.dbg = dbg;
   }
   if (ran) *ran = RingRan{a.segs, a.pool != 0};
-  if (f32_input)
-    conv1_bf16_ring_kernel<true><<<static_cast<unsigned>(N * a.segs), kNT, a.pool ? kLdsPool : kLds, s>>>(a);
+  if (kind == InKind::U8)
+    conv1_bf16_ring_kernel<InKind::U8><<<static_cast<unsigned>(N * a.segs), kNT, a.pool ? kLdsPool : kLds, s>>>(a);
+  else if (kind == InKind::F32)
+    conv1_bf16_ring_kernel<InKind::F32><<<static_cast<unsigned>(N * a.segs), kNT, a.pool ? kLdsPool : kLds, s>>>(a);
   else
-    conv1_bf16_ring_kernel<false><<<static_cast<unsigned>(N * a.segs), kNT, kLds, s>>>(a);
+    conv1_bf16_ring_kernel<InKind::Poly><<<static_cast<unsigned>(N * a.segs), kNT, kLds, s>>>(a);
   if (phases) {  // debug: per-phase s_memtime clocks summed over the tiles, workgroups 0..63 averaged
     unsigned long long h[64 * 8];
     if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(h, a.dbg, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -513,6 +566,18 @@ hipError_t conv1_bf16_ring(const void* xin, int N, const void* wpacked, const fl
     return maxpool_bf16(out.base, N, kHo, kWo, kK, 3, 2, *pool_out, s);
   }
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t conv1_bf16_ring(const void* xin, int N, const void* wpacked, const float* bias, OutViewB out, bool relu,
+                           hipStream_t s, int cus, bool f32_input, const OutViewB* pool_out, RingRan* ran) {
+  return launch_ring(xin, f32_input ? InKind::F32 : InKind::Poly, nullptr, N, wpacked, bias, out, relu, s, cus, pool_out,
+                     ran);
+}
+
+hipError_t conv1_bf16_ring_u8(const uint8_t* xin, const U8Norm& nm, int N, const void* wpacked, const float* bias,
+                              OutViewB out, bool relu, hipStream_t s, int cus, const OutViewB* pool_out, RingRan* ran) {
+  return launch_ring(xin, InKind::U8, &nm, N, wpacked, bias, out, relu, s, cus, pool_out, ran);
 }
 
 }  // namespace anx::hip

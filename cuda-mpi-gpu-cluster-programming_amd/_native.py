@@ -168,6 +168,10 @@ _BF16_SIGS = {
     "anx_full_tap": (_I, [_P, _I, _I, _P, C.POINTER(_SZ), _P]),
     "anx_full_get_knob": (_I, [_P, C.c_char_p, C.POINTER(_I)]),
     "anx_full_last_path": (_I, [_P, C.c_char_p, _SZ]),
+    "anx_full_forward_u8": (_I, [_P, _P, _I, _P, _P]),
+    "anx_full_forward_mark_u8": (_I, [_P, _P, _I, _P, _P]),
+    "anx_full_set_input_norm": (_I, [_P, _P, _P]),
+    "anx_full_last_input": (_I, [_P, C.c_char_p, _SZ]),
 }
 _bf16 = None
 

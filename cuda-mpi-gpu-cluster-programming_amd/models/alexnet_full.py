@@ -5,6 +5,15 @@ on v_mfma_f32_32x32x16_bf16 (csrc/src/hip/conv_bf16.hip, csrc/src/full_engine.cp
 
 The reference itself stops after Block 2; this family exists because the benchmark
 configs name it. FC layers run on the same implicit-GEMM kernel as 1x1 convolutions.
+
+Input is NHWC ``[N,227,227,3]`` on the device, contiguous: ``float32``, or ``torch.uint8`` byte images. A byte
+``b`` of channel ``c`` means ``fmaf(float(b), scale[c], offset[c])`` in fp32 (:func:`anx.ops.decode_u8`), with
+``scale = 1/255`` and ``offset = 0`` unless ``input_norm=(mean, std)`` (0-255 pixel units) sets ``scale = 1/std``,
+``offset = -mean/std``; logits and taps equal those of the float forward of :meth:`AlexNetFull.decode_u8`, bit for
+bit. With the default Conv1 (``bf16_conv1`` 2) and knob ``bf16_u8=1`` the row-band kernel loads the bytes itself
+(``last_input() == "u8_ring"``, no float copy of the input on the device); everywhere else the launch chunk is
+decoded into a workspace that the first such forward allocates (``"u8_decode"``: warm up once before capturing a
+graph) and the float kernels run on it.
 """
 from __future__ import annotations
 
@@ -17,6 +26,7 @@ import torch.nn.functional as F
 from .. import _native as nat
 from ..utils.init import STREAM_EXTRA, uniform
 from ..utils.tuning import apply_knobs, knob_value
+from .alexnet_blocks import norm_scale_offset
 
 LAYERS = ("conv1", "conv2", "conv3", "conv4", "conv5", "fc6", "fc7", "fc8")
 FLOPS_PER_IMAGE = 2.0 * (55 * 55 * 96 * 363 + 27 * 27 * 256 * 2400 + 13 * 13 * 384 * 2304 + 13 * 13 * 384 * 3456 +
@@ -49,7 +59,7 @@ def init_full_weights(seed: int = 0, classes: int = 1000, groups2: int = 1) -> d
 class AlexNetFull:
     def __init__(self, weights: dict | None = None, *, seed: int = 0, classes: int = 1000, device="cuda",
                  max_batch: int = 1, groups2: int = 1, lrn_mode: str = "div_n", knobs: dict | None = None,
-                 lanes: int = 1):
+                 lanes: int = 1, input_norm=None):
         self.classes, self.groups2, self.lrn_mode = classes, groups2, lrn_mode
         self.knobs = {k: knob_value(k, v) for k, v in (knobs or {}).items()}  # e.g. {"bf16_glds": 3}
         self.weights = {k: v.detach().to("cpu", torch.float32).contiguous()
@@ -59,6 +69,8 @@ class AlexNetFull:
             raise ValueError("the bf16 full-AlexNet engine is GPU-only (use reference_forward on the CPU)")
         self._h = None
         self._cap = 0
+        self.input_norm = input_norm
+        self._norm = norm_scale_offset(input_norm, 3)
         if lanes < 1:
             raise ValueError("lanes must be >= 1")
         per_lane = -(-max(1, max_batch) // lanes)
@@ -72,7 +84,8 @@ class AlexNetFull:
         self._lane_streams: list[torch.cuda.Stream] = []
         for _ in range(lanes - 1):
             self._lanes.append(AlexNetFull(self.weights, classes=classes, device=self.device, max_batch=per_lane,
-                                           groups2=groups2, lrn_mode=lrn_mode, knobs=self.knobs))
+                                           groups2=groups2, lrn_mode=lrn_mode, knobs=self.knobs,
+                                           input_norm=input_norm))
             self._lane_streams.append(torch.cuda.Stream(self.device))
 
     def _ensure(self, n):
@@ -91,6 +104,7 @@ class AlexNetFull:
                      0 if self.lrn_mode == "div_n" else 1)
         try:
             apply_knobs(h, self.knobs, full=True)
+            nat.call("anx_full_set_input_norm", h, self._norm[0].data_ptr(), self._norm[1].data_ptr())
         except Exception:
             nat.bf16().anx_full_destroy(h)
             raise
@@ -102,6 +116,33 @@ class AlexNetFull:
         self.knobs[name] = v
         for m in getattr(self, "_lanes", ()):
             m.set_knob(name, v)
+
+    def set_input_norm(self, mean=None, std=None) -> None:
+        """Meaning of byte input from now on (every lane): ``(mean, std)`` in 0-255 pixel units, a number or one
+        per channel each; no arguments: back to ``byte / 255``."""
+        if (mean is None) != (std is None):
+            raise ValueError("set_input_norm takes both mean and std, or neither")
+        norm = None if mean is None else (mean, std)
+        self._norm = norm_scale_offset(norm, 3)
+        self.input_norm = norm
+        nat.call("anx_full_set_input_norm", self._h, self._norm[0].data_ptr(), self._norm[1].data_ptr())
+        for m in getattr(self, "_lanes", ()):
+            m.set_input_norm(mean, std)
+
+    def decode_u8(self, x: torch.Tensor) -> torch.Tensor:
+        """The float32 image this model's byte input means (:func:`anx.ops.decode_u8` with its scale / offset)."""
+        from ..ops import decode_u8
+        return decode_u8(x, self._norm[0], self._norm[1])
+
+    def last_input(self, lane: int = 0) -> str | None:
+        """How the last forward of this model's engine (``lane`` > 0: that side lane's) fed Conv1: ``"f32"`` (float
+        input), ``"u8_ring"`` (the row-band Conv1 loaded the bytes), ``"u8_decode"`` (decode kernel, then the float
+        path); ``None`` before the first. Recorded at the launch; reading it makes no device call."""
+        if lane:
+            return self._lanes[lane - 1].last_input()
+        buf = C.create_string_buffer(32)
+        nat.call("anx_full_last_input", self._h, buf, len(buf))
+        return buf.value.decode() or None
 
     def close(self):
         for m in getattr(self, "_lanes", ()):
@@ -120,9 +161,9 @@ class AlexNetFull:
     def _check(self, x: torch.Tensor, out: torch.Tensor | None) -> torch.Tensor:
         """The engine reads x and writes out through raw pointers: both must be exactly what the
         kernels assume (shape, dtype, contiguity, device)."""
-        if (x.dim() != 4 or tuple(x.shape[1:]) != (227, 227, 3) or x.dtype != torch.float32 or not x.is_contiguous()
-                or x.device != self.device):
-            raise ValueError(f"expected contiguous fp32 NHWC [N,227,227,3] on {self.device}, got "
+        if (x.dim() != 4 or tuple(x.shape[1:]) != (227, 227, 3) or x.dtype not in (torch.float32, torch.uint8)
+                or not x.is_contiguous() or x.device != self.device):
+            raise ValueError(f"expected contiguous fp32 (or uint8: byte images) NHWC [N,227,227,3] on {self.device}, got "
                              f"{tuple(x.shape)} {x.dtype} on {x.device}")
         shape = (x.shape[0], self.classes)
         if out is None:
@@ -134,13 +175,14 @@ class AlexNetFull:
         return out
 
     def forward(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        """x: [N,227,227,3] fp32 NHWC on the device -> logits [N, classes] fp32."""
+        """x: [N,227,227,3] fp32 (or uint8: byte images) NHWC on the device -> logits [N, classes] fp32."""
         y = self._check(x, out)
         N = x.shape[0]
+        fwd = "anx_full_forward_u8" if x.dtype == torch.uint8 else "anx_full_forward"
         L = 1 + len(self._lanes)
         if L == 1 or N < L:
             self._ensure(N)
-            nat.call("anx_full_forward", self._h, x.data_ptr(), N, y.data_ptr(), nat.stream_ptr(self.device))
+            nat.call(fwd, self._h, x.data_ptr(), N, y.data_ptr(), nat.stream_ptr(self.device))
             return y
         bounds = [N * i // L for i in range(L + 1)]
         cur = torch.cuda.current_stream(self.device)
@@ -149,7 +191,7 @@ class AlexNetFull:
             with torch.cuda.stream(st):
                 self._lanes[i - 1].forward(x[bounds[i]:bounds[i + 1]], y[bounds[i]:bounds[i + 1]])
         self._ensure(bounds[1])
-        nat.call("anx_full_forward", self._h, x.data_ptr(), bounds[1], y.data_ptr(), nat.stream_ptr(self.device))
+        nat.call(fwd, self._h, x.data_ptr(), bounds[1], y.data_ptr(), nat.stream_ptr(self.device))
         for st in self._lane_streams:
             cur.wait_stream(st)  # join
         return y
@@ -186,6 +228,8 @@ class AlexNetFull:
                 if i > 0:
                     nat.call("anx_full_wait_mark", engines[i - 1]._h, st.cuda_stream)
             fn = "anx_full_forward_mark" if fresh and i + 1 < L else "anx_full_forward"
+            if x.dtype == torch.uint8:
+                fn += "_u8"
             with torch.cuda.stream(st):
                 if pre_lane is not None:
                     pre_lane(i, lo, hi)

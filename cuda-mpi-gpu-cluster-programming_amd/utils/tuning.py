@@ -34,7 +34,10 @@ Names and values:
   compiler's schedule); ``lrn_wgs`` (256, the default: grid cap of the pool2-merge + LRN kernel, its waves
   walking the remaining pixels; 0 = one wave per pixel pair; same bits); ``conv1_u8`` (byte input where the
   one-kernel Conv1 runs: 0, the default by measurement = the decode kernel into a workspace and then the float
-  kernel, 1 = the kernel loads and decodes the bytes itself; same bits).
+  kernel, 1 = the kernel loads and decodes the bytes itself; same bits); ``bf16_u8`` (0 / 1: byte input of the bf16
+  full model where Conv1 is the row-band kernel on the image, ``bf16_conv1`` 2: 1 = that kernel loads and decodes
+  the bytes itself, 0 = the decode kernel into a workspace and then the float kernel; same bits; the default is
+  set by measurement, ``profiles/bf16_u8_input/``).
 """
 from __future__ import annotations
 
@@ -45,7 +48,8 @@ from .. import _native as nat
 ALGOS = {"auto": 0, "direct": 1, "winograd": 2}
 KNOBS = ("conv1_algo", "conv2_algo", "chunk1", "chunk2", "force_vec4", "force_scalar", "bf16_glds", "bf16_big",
          "bf16_lrn_tile", "bf16_conv1", "bf16_pool1", "bf16_fc_cfg", "bf16_fc_minkt", "conv1_occ", "conv2_occ", "conv1_band", "fuse_pool1", "conv1_sub", "conv2_sub",
-         "conv1_fused", "conv1_pool", "conv1_u8", "conv2_pool", "conv2_tile", "conv2_sched", "conv2_in_pg", "lrn_wgs")
+         "conv1_fused", "conv1_pool", "conv1_u8", "conv2_pool", "conv2_tile", "conv2_sched", "conv2_in_pg", "lrn_wgs",
+         "bf16_u8")
 
 
 def knob_value(name: str, value) -> int:
@@ -56,6 +60,8 @@ def knob_value(name: str, value) -> int:
         if value not in ALGOS:
             raise ValueError(f"{name} must be one of {sorted(ALGOS)}")
         return ALGOS[value]
+    if name == "bf16_u8" and int(value) not in (0, 1):
+        raise ValueError(f"{name} must be 0 or 1")
     return int(value)
 
 
