@@ -7,6 +7,7 @@
 #include <cstring>
 #include <vector>
 
+#include "anx/device.hpp"
 #include "anx/knobs.hpp"
 #include "anx/ops.hpp"
 #include "anx/shapes.hpp"
@@ -144,7 +145,6 @@ class FullEngine {
  public:
   FullEngine(const FullWeights& w, int classes, int max_batch, int groups2 = 1, LrnMode lrn = LrnMode::DivN,
              const Knobs& k = default_knobs());
-  ~FullEngine();
   FullEngine(const FullEngine&) = delete;
   FullEngine& operator=(const FullEngine&) = delete;
   // x: [N,227,227,3] fp32 device; logits: [N,classes] fp32 device.
@@ -164,7 +164,9 @@ class FullEngine {
   // forward(..., mark = true) records this engine's mark event on `s` once Conv2 + Pool2/LRN of the
   // first chunk are enqueued (about half of the forward): wait_mark makes another stream wait for it,
   // which staggers free-running lanes (AlexNetFull.forward_async) by half a forward.
-  hipError_t wait_mark(hipStream_t s) const { return mark_ ? hipStreamWaitEvent(s, mark_, 0) : hipErrorInvalidValue; }
+  hipError_t wait_mark(hipStream_t s) const {
+    return mark_ ? hipStreamWaitEvent(s, mark_.get(), 0) : hipErrorInvalidValue;
+  }
   int classes() const { return classes_; }
   int max_batch() const { return max_batch_; }
   Knobs& knobs() { return k_; }  // read at every launch (bf16_glds, bf16_big)
@@ -177,12 +179,12 @@ class FullEngine {
   const FullPathRecord& last_path() const { return path_; }
 
  private:
-  hipEvent_t mark_ = nullptr;
+  HipEvent mark_;
   struct Layer {
     int C, K, F, S, groups;
-    void* wp = nullptr;
-    int* koff = nullptr;
-    float* bias = nullptr;
+    DevBuf<uint16_t> wp;  // bf16 packed for tile variant `key`
+    DevBuf<int> koff;
+    DevBuf<float> bias;
     int key = -1;
     std::vector<float> host;  // KCFF fp32 (re-pack when the tile variant changes)
   };
@@ -191,7 +193,7 @@ class FullEngine {
   // the one layer chain: exactly one of xf (floats) / xu (bytes) is set
   hipError_t run(const float* xf, const uint8_t* xu, int N, float* logits, hipStream_t s, bool mark);
   hip::U8Norm norm_{3, {1.f / 255.f, 1.f / 255.f, 1.f / 255.f}, {0.f, 0.f, 0.f}};  // byte input: scale / offset
-  float* xdec_ = nullptr;          // byte input decoded to fp32 (u8_decode), chunk_ images, allocated on first need
+  DevBuf<float> xdec_;             // byte input decoded to fp32 (u8_decode), chunk_ images, allocated on first need
   const char* input_ = nullptr;    // last_input()
   Layer L_[8];
   FullPathRecord path_;
@@ -200,10 +202,18 @@ class FullEngine {
   int cus_ = 256;  // compute units (the wide-tile kernel's cost model)
   LrnMode lrn_;
   bool poly1_ = false;  // Conv1 as a stride-1 3x3 conv over the 48-channel polyphase image (ANX_FULL_CONV1)
-  void* w1ring_ = nullptr;  // Conv1 weights packed for conv1_bf16_ring (poly1_ only)
-  void *xb_ = nullptr, *c1_ = nullptr, *q2_ = nullptr, *c2_ = nullptr, *q3_ = nullptr, *q4_ = nullptr,
-       *q5_ = nullptr, *c5_ = nullptr, *f6_ = nullptr, *f7_ = nullptr, *f8_ = nullptr;
-  float* ws_ = nullptr;  // split-K partial slabs of the FC layers (sized for every batch <= chunk_)
+  DevBuf<uint16_t> w1ring_;  // Conv1 weights packed for conv1_bf16_ring (poly1_ only)
+  // The bf16 activation buffers, chunk_ images each, in tap()'s order. kActs is the one table of their sizes:
+  // the constructor's allocations and memsets and tap() derive from it.
+  enum Act { kC1, kQ2, kC2, kQ3, kQ4, kQ5, kC5, kF6, kF7, kF8, kXb, kNumActs };
+  struct ActSpec {
+    size_t elems;  // per image
+    bool window;   // zero-bordered window: zeroed once, kernels write the interior only
+  };
+  static const ActSpec kActs[kNumActs];
+  DevBuf<uint16_t> act_[kNumActs];
+  void* a(Act i) const { return act_[i].get(); }
+  DevBuf<float> ws_;  // split-K partial slabs of the FC layers (sized for every batch <= chunk_)
 };
 
 }  // namespace anx

@@ -31,6 +31,12 @@ const char* anx_last_error(void);
 void anx_set_last_error(const char* msg); /* for the companion libraries (libanx_dist) */
 int anx_abi_version(void);
 int anx_device_count(void);
+/* Diagnostics of the device owners (anx/device.hpp). out: live device buffers, live device bytes, live
+ * streams + events, cumulative device allocation calls of this process. */
+int anx_device_live(size_t out[4]);
+/* Test hook: the nth next device allocation of this process (1-based) fails with hipErrorOutOfMemory
+ * without calling HIP, then the hook disarms itself; 0 disarms it. */
+int anx_device_fail_alloc(int nth);
 void anx_default_blocks(anx_block_c* b1, anx_block_c* b2);
 
 /* ---- planner ---- */

@@ -100,8 +100,7 @@ class DeviceComm {
   virtual void abort() {}
 
  protected:
-  void init_sync();  // creates ev_ (call from the implementations' constructors)
-  hipEvent_t ev_ = nullptr;
+  virtual hipEvent_t sync_event() const = 0;  // the implementation's event behind after / before / after_comm
 };
 // Collective over `boot` (every rank constructs its communicators in the same order).
 std::unique_ptr<DeviceComm> make_rccl_comm(HostComm& boot, int device);

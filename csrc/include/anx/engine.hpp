@@ -12,6 +12,7 @@
 
 #include <vector>
 
+#include "anx/device.hpp"
 #include "anx/knobs.hpp"
 #include "anx/ops.hpp"
 #include "anx/plan.hpp"
@@ -51,7 +52,6 @@ class BlocksEngine {
   // k: kernel selection and tuning of this engine (default_knobs(): built-in defaults + ANX_* env).
   BlocksEngine(const BlockSpec& b1, const BlockSpec& b2, int H, int W, const HostWeights& w, int max_batch,
                Impl impl = Impl::Mfma, const Knobs& k = default_knobs());
-  ~BlocksEngine();
   BlocksEngine(const BlocksEngine&) = delete;
   BlocksEngine& operator=(const BlocksEngine&) = delete;
 
@@ -109,8 +109,14 @@ class BlocksEngine {
 
  private:
   void prepare();
-  hipError_t pack1(const hip::ConvPlan& p);  // direct-path packed weights for plan p (no-op when current)
-  hipError_t pack2(const hip::ConvPlan& p);
+  // direct-path packed weights of one conv for a plan (key: the plan's variant | taps4 << 8)
+  struct Packed {
+    DevBuf<float> w;
+    DevBuf<int> koff;
+    int key = -1;
+  };
+  // packs w_kcff for plan p into pk (no-op when current). A failure leaves the old pair and key intact.
+  hipError_t pack(Packed& pk, const std::vector<float>& w_kcff, const hip::ConvPlan& p);
   hipError_t ensure_window(const TilePlan& t, int N, hipStream_t s);
   // An input image batch: floats, or bytes (u8 != nullptr)
   struct In {
@@ -142,26 +148,24 @@ class BlocksEngine {
   PathRecord path_;
   const char* input_ = nullptr;  // last_input()
   hip::U8Norm norm_{};           // byte input: scale / offset per channel (C == 0: C0 too large for byte input)
-  float* xdec_ = nullptr;        // decoded launch chunk (byte input on the float paths)
+  DevBuf<float> xdec_;           // decoded launch chunk (byte input on the float paths)
   size_t xdec_cap_ = 0;
   int wq_;     // padded conv2 input width
   int full1_ = 0, full2_ = 0;  // conv1 / conv2 rows of the whole-image tile (use_winograd's "full image")
   // device buffers
-  float *w1_ = nullptr, *b1d_ = nullptr, *w2_ = nullptr, *b2d_ = nullptr;  // KCFF (direct path)
-  float *w1p_ = nullptr, *w2p_ = nullptr;                                  // packed (MFMA path)
-  int *koff1_ = nullptr, *koff2_ = nullptr;
-  float *c1_ = nullptr, *q2_ = nullptr, *c2_ = nullptr;  // workspace
+  DevBuf<float> w1_, b1d_, w2_, b2d_;  // KCFF (direct path)
+  Packed p1_, p2_;                     // packed (MFMA path)
+  DevBuf<float> c1_, q2_, c2_;         // workspace
   size_t q2_cap_ = 0;
   // zero-state cache for the conv2 window
   int win_lo_ = 1 << 30, win_hi_ = -(1 << 30), win_n_ = -1;
-  int plan_key1_ = -1, plan_key2_ = -1;
   // Winograd conv2: transformed weights [49][K][C/groups] + V workspace
-  float *u2w_ = nullptr, *wv_ = nullptr;
+  DevBuf<float> u2w_, wv_;
   size_t wv_cap_ = 0;
   int u2_m_ = 3;       // Winograd output tile of u2w_ / wv_ (Knobs::conv2_tile when eligible)
   int tile2() const;   // the tile the knobs ask for and Conv2's shape allows
   // Winograd conv1: transformed polyphase weights + V workspace (full-height tiles of chunk_ images)
-  float *u1w_ = nullptr, *wv1_ = nullptr;
+  DevBuf<float> u1w_, wv1_;
   size_t wv1_cap_ = 0;
   std::vector<float> w1h_, w2h_;  // KCFF host copies for re-packing on geometry change
 };

@@ -121,7 +121,20 @@ const char* anx_last_error(void) { return g_err.c_str(); }
 // 2: byte input (anx_*_u8, anx_*_set_input_norm, anx_engine_last_input)
 // 3: byte input of the bf16 full model (anx_full_forward_u8, anx_full_forward_mark_u8, anx_full_set_input_norm,
 //    anx_full_last_input; knob bf16_u8)
-int anx_abi_version(void) { return 3; }
+// 4: device-owner diagnostics (anx_device_live, anx_device_fail_alloc)
+int anx_abi_version(void) { return 4; }
+
+int anx_device_live(size_t out[4]) {
+  if (!out) return fail("anx_device_live: no buffer");
+  anx::device_live(out);
+  return 0;
+}
+
+int anx_device_fail_alloc(int nth) {
+  if (nth < 0) return fail("anx_device_fail_alloc: nth < 0");
+  anx::device_fail_alloc(nth);
+  return 0;
+}
 
 int anx_device_count(void) {
   int n = 0;
@@ -479,20 +492,15 @@ int anx_conv1_wino(const float* x, int N, int Hin, int W, const float* w_kcff, i
     const auto w = anx::hip::make_conv1_wino_plan(N, Hin, W, K, F);
     std::vector<float> u;
     anx::hip::conv1_wino_weights_host(K, F, w_kcff, u);
-    float *dv = nullptr, *du = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&dv), std::max<size_t>(anx::hip::conv1_wino_v_floats(w), 1) * 4) != hipSuccess)
+    anx::DevBuf<float> vbuf, ubuf;
+    if (vbuf.try_alloc(anx::hip::conv1_wino_v_floats(w)) != hipSuccess || ubuf.try_alloc(u.size()) != hipSuccess)
       return fail("anx_conv1_wino: hipMalloc");
-    if (hipMalloc(reinterpret_cast<void**>(&du), u.size() * 4) != hipSuccess) {
-      (void)hipFree(dv);
-      return fail("anx_conv1_wino: hipMalloc");
-    }
+    float *const dv = vbuf.get(), *const du = ubuf.get();
     hipError_t e = hipMemcpy(du, u.data(), u.size() * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess)
       e = anx::hip::conv1_wino(w, x, dv, du, bias, anx::hip::OutView{y, w.H1, w.W1, K, 0, 0, 0}, relu != 0, S(stream),
                                anx::default_knobs());
-    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));  // the workspaces are freed below
-    (void)hipFree(dv);
-    (void)hipFree(du);
+    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));  // the workspaces are freed on return
     return hip_status(e, "conv1_wino");
   });
 }
@@ -505,21 +513,16 @@ int anx_conv2_wino_tile(const float* x, int N, int Hq, int Wq, int C, const floa
     const auto w = anx::hip::make_wino_plan(N, Hq, Wq, C, K, groups, m);
     std::vector<float> u;
     anx::hip::wino_transform_weights_host(w, w_kcff, u);
-    float *dv = nullptr, *du = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&dv), std::max<size_t>(anx::hip::wino_v_floats(w), 1) * 4) != hipSuccess)
+    anx::DevBuf<float> vbuf, ubuf;
+    if (vbuf.try_alloc(anx::hip::wino_v_floats(w)) != hipSuccess || ubuf.try_alloc(u.size()) != hipSuccess)
       return fail("anx_conv2_wino: hipMalloc");
-    if (hipMalloc(reinterpret_cast<void**>(&du), u.size() * 4) != hipSuccess) {
-      (void)hipFree(dv);
-      return fail("anx_conv2_wino: hipMalloc");
-    }
+    float *const dv = vbuf.get(), *const du = ubuf.get();
     hipError_t e = hipMemcpy(du, u.data(), u.size() * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = anx::hip::wino_input(w, x, dv, S(stream));
     if (e == hipSuccess)
       e = anx::hip::wino_conv2(w, dv, du, bias, anx::hip::OutView{y, w.Ho, w.Wo, K, 0, 0, 0}, relu != 0, S(stream),
                                anx::default_knobs());
-    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));  // the workspaces are freed below
-    (void)hipFree(dv);
-    (void)hipFree(du);
+    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));  // the workspaces are freed on return
     return hip_status(e, "conv2_wino");
   });
 }

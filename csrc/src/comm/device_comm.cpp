@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "anx/comm.hpp"
+#include "anx/device.hpp"
 
 namespace anx {
 
@@ -22,25 +23,20 @@ namespace {
 void nccl_check(ncclResult_t r, const char* what) {
   if (r != ncclSuccess) throw std::runtime_error(std::string("RCCL ") + what + ": " + ncclGetErrorString(r));
 }
-void hip_check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("HIP ") + what + ": " + hipGetErrorString(e));
-}
 }  // namespace
 
-void DeviceComm::init_sync() { hip_check(hipEventCreateWithFlags(&ev_, hipEventDisableTiming), "hipEventCreate"); }
-
 void DeviceComm::after(hipStream_t compute) {
-  hip_check(hipEventRecord(ev_, compute), "hipEventRecord");
-  hip_check(hipStreamWaitEvent(stream(), ev_, 0), "hipStreamWaitEvent");
+  hip_check(hipEventRecord(sync_event(), compute), "hipEventRecord");
+  hip_check(hipStreamWaitEvent(stream(), sync_event(), 0), "hipStreamWaitEvent");
 }
 void DeviceComm::before(hipStream_t compute) {
-  hip_check(hipEventRecord(ev_, stream()), "hipEventRecord");
-  hip_check(hipStreamWaitEvent(compute, ev_, 0), "hipStreamWaitEvent");
+  hip_check(hipEventRecord(sync_event(), stream()), "hipEventRecord");
+  hip_check(hipStreamWaitEvent(compute, sync_event(), 0), "hipStreamWaitEvent");
 }
 void DeviceComm::after_comm(DeviceComm& other) {
   if (&other == this) return;
-  hip_check(hipEventRecord(other.ev_, other.stream()), "hipEventRecord");
-  hip_check(hipStreamWaitEvent(stream(), other.ev_, 0), "hipStreamWaitEvent");
+  hip_check(hipEventRecord(other.sync_event(), other.stream()), "hipEventRecord");
+  hip_check(hipStreamWaitEvent(stream(), other.sync_event(), 0), "hipStreamWaitEvent");
 }
 
 // ---------------------------------------------------------------------------------------------- RCCL
@@ -56,13 +52,11 @@ class RcclComm final : public DeviceComm {
     ncclComm_t c;
     nccl_check(ncclCommInitRank(&c, boot.size(), id, boot.rank()), "ncclCommInitRank");
     comm_ = c;
-    hip_check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
-    init_sync();
+    stream_ = HipStream::create();
+    ev_ = HipEvent::create(hipEventDisableTiming);
   }
   ~RcclComm() override {
-    if (comm_) ncclCommDestroy(comm_);
-    if (ev_) (void)hipEventDestroy(ev_);
-    if (stream_) (void)hipStreamDestroy(stream_);
+    if (comm_) ncclCommDestroy(comm_);  // then the event, then the stream (member order)
   }
   const char* kind() const override { return "rccl"; }
   hipStream_t stream() const override { return stream_; }
@@ -83,8 +77,10 @@ class RcclComm final : public DeviceComm {
   }
 
  private:
+  hipEvent_t sync_event() const override { return ev_; }
   ncclComm_t comm_ = nullptr;
-  hipStream_t stream_ = nullptr;
+  HipStream stream_;  // declared before the event: destroyed after it
+  HipEvent ev_;
 };
 
 // ------------------------------------------------------------------------------------------ loopback
@@ -99,10 +95,11 @@ class LoopbackComm final : public DeviceComm {
     int can = 0;
     if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device) != hipSuccess || !can)
       throw std::runtime_error("loopback device comm: the device lacks hipStreamWaitValue32");
-    hip_check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
-    init_sync();
+    stream_ = HipStream::create();
+    ev_ = HipEvent::create(hipEventDisableTiming);
     const size_t bytes = static_cast<size_t>(np_) * 2 * sizeof(uint32_t);
-    hip_check(hipMalloc(reinterpret_cast<void**>(&flags_), bytes), "hipMalloc flags");
+    flags_own_ = DevBuf<uint32_t>(static_cast<size_t>(np_) * 2);
+    flags_ = flags_own_.get();
     hip_check(hipMemset(flags_, 0, bytes), "hipMemset flags");
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
     flags_of_.assign(np_, nullptr);
@@ -130,9 +127,10 @@ class LoopbackComm final : public DeviceComm {
     }
     for (void* p : opened_) (void)hipIpcCloseMemHandle(p);
     for (auto& kv : peer_bufs_) (void)hipIpcCloseMemHandle(kv.second);
-    if (flags_) (void)hipFree(flags_);
-    if (ev_) (void)hipEventDestroy(ev_);
-    if (stream_) (void)hipStreamDestroy(stream_);
+    // explicitly, in this order: peers unmapped and past the barrier above, then the owner frees
+    flags_own_.reset();
+    ev_.reset();
+    stream_.reset();
   }
   const char* kind() const override { return "loopback"; }
   // RCCL's ncclCommAbort equivalent: a stream parked in hipStreamWaitValue32 on a peer that died would
@@ -262,8 +260,11 @@ class LoopbackComm final : public DeviceComm {
 
   HostComm& hc_;
   int rank_, np_;
-  hipStream_t stream_ = nullptr;
-  uint32_t* flags_ = nullptr;
+  hipEvent_t sync_event() const override { return ev_; }
+  HipStream stream_;
+  HipEvent ev_;
+  DevBuf<uint32_t> flags_own_;
+  uint32_t* flags_ = nullptr;  // flags_own_'s words
   std::vector<uint32_t*> flags_of_;
   std::vector<void*> opened_;
   std::map<std::string, void*> peer_bufs_;

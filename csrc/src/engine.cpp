@@ -13,32 +13,7 @@
 #include "anx/trace.hpp"
 #include "anx/upload.hpp"
 
-#define ANX_TRY(expr)                          \
-  do {                                         \
-    hipError_t _e = (expr);                    \
-    if (_e != hipSuccess) return _e;           \
-  } while (0)
-
 namespace anx {
-
-namespace {
-void check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-template <class T>
-T* dev_alloc(size_t n) {
-  void* p = nullptr;
-  if (n == 0) n = 1;
-  check(hipMalloc(&p, n * sizeof(T)), "hipMalloc");
-  return static_cast<T*>(p);
-}
-template <class T>
-T* dev_upload(const std::vector<T>& h) {
-  T* d = dev_alloc<T>(h.size());
-  check(upload_h2d(d, h.data(), h.size() * sizeof(T)), "upload H2D");  // pinned staging (anx/upload.hpp)
-  return d;
-}
-}  // namespace
 
 void init_const(HostWeights& w, const BlockSpec& b1, const BlockSpec& b2, float wv, float bv) {
   const ConvSpec &c1 = b1.conv, &c2 = b2.conv;
@@ -99,15 +74,15 @@ BlocksEngine::BlocksEngine(const BlockSpec& b1, const BlockSpec& b2, int H, int 
   const double t0 = phases ? ms() : 0;
   w1h_ = w.w1;
   w2h_ = w.w2;
-  w1_ = dev_upload(w.w1);
-  b1d_ = dev_upload(w.b1);
-  w2_ = dev_upload(w.w2);
-  b2d_ = dev_upload(w.b2);
+  w1_ = DevBuf<float>::upload(w.w1);
+  b1d_ = DevBuf<float>::upload(w.b1);
+  w2_ = DevBuf<float>::upload(w.w2);
+  b2d_ = DevBuf<float>::upload(w.b2);
   const double t1 = phases ? ms() : 0;
-  c1_ = dev_alloc<float>(static_cast<size_t>(chunk_) * d_.H1 * d_.W1 * d_.C1);
+  c1_ = DevBuf<float>(static_cast<size_t>(chunk_) * d_.H1 * d_.W1 * d_.C1);
   q2_cap_ = static_cast<size_t>(max_batch) * (d_.Hp1 + 2 * b2.conv.P) * wq_ * d_.C1;
-  q2_ = dev_alloc<float>(q2_cap_);
-  c2_ = dev_alloc<float>(static_cast<size_t>(chunk_) * d_.H2 * d_.W2 * d_.C2);
+  q2_ = DevBuf<float>(q2_cap_);
+  c2_ = DevBuf<float>(static_cast<size_t>(chunk_) * d_.H2 * d_.W2 * d_.C2);
   const double t2 = phases ? ms() : 0;
   prepare();
   if (phases)
@@ -123,28 +98,24 @@ BlocksEngine::BlocksEngine(const BlockSpec& b1, const BlockSpec& b2, int H, int 
 void BlocksEngine::prepare() {
   if (impl_ != Impl::Mfma) return;
   const ConvSpec &k1 = b1_.conv, &k2 = b2_.conv;
-  if (u1w_ == nullptr && hip::conv1_wino_eligible(k1.C, k1.K, k1.F, k1.S, k1.P, k1.groups) &&
+  if (!u1w_ && hip::conv1_wino_eligible(k1.C, k1.K, k1.F, k1.S, k1.P, k1.groups) &&
       use_winograd(k_.conv1_algo, max_batch_, d_.H1, d_.H1)) {
     const hip::Conv1WinoPlan wp = hip::make_conv1_wino_plan(chunk_, d_.H, d_.W, k1.K, k1.F);
     std::vector<float> u;
     hip::conv1_wino_weights_host(k1.K, k1.F, w1h_.data(), u);
     // both buffers or neither (a failed allocation leaves the path off and retryable)
-    float* v = dev_alloc<float>(hip::conv1_wino_v_floats(wp));
-    try {
-      u1w_ = dev_upload(u);
-    } catch (...) {
-      (void)hipFree(v);
-      throw;
-    }
+    DevBuf<float> v(hip::conv1_wino_v_floats(wp));
+    DevBuf<float> uw = DevBuf<float>::upload(u);
     wv1_cap_ = hip::conv1_wino_v_floats(wp);
-    wv1_ = v;
+    wv1_ = std::move(v);
+    u1w_ = std::move(uw);
   }
-  if (u2w_ != nullptr && u2_m_ != tile2()) {  // the tile knob changed: other transformed weights / workspace
-    for (float** q : {&u2w_, &wv_})
-      if (*q) (void)hipFree(*q), *q = nullptr;
+  if (u2w_ && u2_m_ != tile2()) {  // the tile knob changed: other transformed weights / workspace
+    u2w_.reset();
+    wv_.reset();
     wv_cap_ = 0;
   }
-  if (u2w_ == nullptr && hip::wino_eligible(k2.F, k2.S, d_.C1, d_.C2, k2.groups) &&
+  if (!u2w_ && hip::wino_eligible(k2.F, k2.S, d_.C1, d_.C2, k2.groups) &&
       use_winograd(k_.conv2_algo, max_batch_, d_.H2, d_.H2)) {
     // Winograd workspace for a full-height window of chunk_ images (row tiles need less)
     const hip::WinoPlan wp = hip::make_wino_plan(chunk_, d_.Hp1 + 2 * k2.P, wq_, d_.C1, d_.C2, k2.groups, tile2());
@@ -152,15 +123,11 @@ void BlocksEngine::prepare() {
     if (hip::wino_v_floats(wp) < (1UL << 31)) {
       std::vector<float> u;
       hip::wino_transform_weights_host(wp, w2h_.data(), u);
-      float* v = dev_alloc<float>(hip::wino_v_floats(wp));
-      try {
-        u2w_ = dev_upload(u);
-      } catch (...) {
-        (void)hipFree(v);
-        throw;
-      }
+      DevBuf<float> v(hip::wino_v_floats(wp));
+      DevBuf<float> uw = DevBuf<float>::upload(u);
       wv_cap_ = hip::wino_v_floats(wp);
-      wv_ = v;
+      wv_ = std::move(v);
+      u2w_ = std::move(uw);
     }
   }
   // direct path: the full-image launch of min(max_batch, the Auto crossover) images
@@ -172,12 +139,15 @@ void BlocksEngine::prepare() {
   const double tp = phases ? ms() : 0;
   const int n = std::max(1, std::min(max_batch_, chunk_));
   const int nd = k_.conv1_algo == ConvAlgo::Direct ? n : std::min(n, 8);
-  if (!use_winograd(k_.conv1_algo, nd, d_.H1, d_.H1) || wv1_ == nullptr)
-    (void)pack1(hip::make_conv_plan(nd, d_.H, d_.W, d_.C0, k1.K, k1.F, k1.S, k1.groups, k_.force_vec4, k_.force_scalar));
+  if (!use_winograd(k_.conv1_algo, nd, d_.H1, d_.H1) || !wv1_)
+    hip_check(pack(p1_, w1h_, hip::make_conv_plan(nd, d_.H, d_.W, d_.C0, k1.K, k1.F, k1.S, k1.groups, k_.force_vec4,
+                                                  k_.force_scalar)),
+              "pack conv1 weights");
   const int nd2 = k_.conv2_algo == ConvAlgo::Direct ? n : std::min(n, 8);
-  if (!use_winograd(k_.conv2_algo, nd2, d_.H2, d_.H2) || wv_ == nullptr)
-    (void)pack2(hip::make_conv_plan(nd2, d_.Hp1 + 2 * k2.P, wq_, d_.C1, k2.K, k2.F, k2.S, k2.groups, k_.force_vec4,
-                                    k_.force_scalar));
+  if (!use_winograd(k_.conv2_algo, nd2, d_.H2, d_.H2) || !wv_)
+    hip_check(pack(p2_, w2h_, hip::make_conv_plan(nd2, d_.Hp1 + 2 * k2.P, wq_, d_.C1, k2.K, k2.F, k2.S, k2.groups,
+                                                  k_.force_vec4, k_.force_scalar)),
+              "pack conv2 weights");
   if (phases) std::fprintf(stderr, "ANX_ENGINE_PHASES direct-path packing %.3f ms\n", ms() - tp);
 }
 
@@ -201,49 +171,30 @@ int BlocksEngine::set_knob(const char* name, int value) {
   return 0;
 }
 
-hipError_t BlocksEngine::pack1(const hip::ConvPlan& p) {
+hipError_t BlocksEngine::pack(Packed& pk, const std::vector<float>& w_kcff, const hip::ConvPlan& p) {
   const int key = p.variant | (p.taps4 << 8);
-  if (key == plan_key1_) return hipSuccess;
+  if (key == pk.key) return hipSuccess;
   std::vector<float> packed;
   std::vector<int> koff;
-  hip::pack_conv_weights_host(p, w1h_.data(), packed, koff);
-  if (w1p_) ANX_TRY(hipFree(w1p_));
-  if (koff1_) ANX_TRY(hipFree(koff1_));
-  w1p_ = dev_upload(packed);
-  koff1_ = dev_upload(koff);
-  plan_key1_ = key;
+  hip::pack_conv_weights_host(p, w_kcff.data(), packed, koff);
+  // the new pair first, then commit it with its key
+  DevBuf<float> w;
+  DevBuf<int> ko;
+  ANX_TRY(w.try_alloc(packed.size()));
+  ANX_TRY(ko.try_alloc(koff.size()));
+  ANX_TRY(upload_h2d(w.get(), packed.data(), packed.size() * sizeof(float)));
+  ANX_TRY(upload_h2d(ko.get(), koff.data(), koff.size() * sizeof(int)));
+  pk.w = std::move(w);
+  pk.koff = std::move(ko);
+  pk.key = key;
   return hipSuccess;
-}
-
-hipError_t BlocksEngine::pack2(const hip::ConvPlan& p) {
-  const int key = p.variant | (p.taps4 << 8);
-  if (key == plan_key2_) return hipSuccess;
-  std::vector<float> packed;
-  std::vector<int> koff;
-  hip::pack_conv_weights_host(p, w2h_.data(), packed, koff);
-  if (w2p_) ANX_TRY(hipFree(w2p_));
-  if (koff2_) ANX_TRY(hipFree(koff2_));
-  w2p_ = dev_upload(packed);
-  koff2_ = dev_upload(koff);
-  plan_key2_ = key;
-  return hipSuccess;
-}
-
-BlocksEngine::~BlocksEngine() {
-  for (void* p : {static_cast<void*>(w1_), static_cast<void*>(b1d_), static_cast<void*>(w2_),
-                  static_cast<void*>(b2d_), static_cast<void*>(w1p_), static_cast<void*>(w2p_),
-                  static_cast<void*>(koff1_), static_cast<void*>(koff2_), static_cast<void*>(c1_),
-                  static_cast<void*>(q2_), static_cast<void*>(c2_), static_cast<void*>(u2w_),
-                  static_cast<void*>(wv_), static_cast<void*>(u1w_), static_cast<void*>(wv1_),
-                  static_cast<void*>(xdec_)})
-    if (p) (void)hipFree(p);
 }
 
 hipError_t BlocksEngine::ensure_window(const TilePlan& t, int N, hipStream_t s) {
   if (t.q.lo == win_lo_ && t.q.hi == win_hi_ && N <= win_n_) return hipSuccess;
   const size_t n = static_cast<size_t>(N) * t.q.size() * wq_ * d_.C1;
   if (n > q2_cap_) return hipErrorInvalidValue;
-  ANX_TRY(hipMemsetAsync(q2_, 0, n * sizeof(float), s));
+  ANX_TRY(hipMemsetAsync(q2_.get(), 0, n * sizeof(float), s));
   win_lo_ = t.q.lo;
   win_hi_ = t.q.hi;
   win_n_ = N;
@@ -251,7 +202,7 @@ hipError_t BlocksEngine::ensure_window(const TilePlan& t, int N, hipStream_t s) 
 }
 
 float* BlocksEngine::q2_row_ptr(const TilePlan& t, int n, int r) {
-  return q2_ + static_cast<size_t>(n) * q2_image_stride_floats(t) + static_cast<size_t>(r - t.q.lo) * q2_row_floats();
+  return q2_.get() + static_cast<size_t>(n) * q2_image_stride_floats(t) + static_cast<size_t>(r - t.q.lo) * q2_row_floats();
 }
 
 void BlocksEngine::set_input_norm(const float* scale, const float* offset) {
@@ -268,33 +219,33 @@ hipError_t BlocksEngine::decode_chunk(const uint8_t* x, size_t elems, hipStream_
       return hipErrorStreamCaptureUnsupported;
     const size_t cap = static_cast<size_t>(chunk_) * d_.H * d_.W * d_.C0;
     if (elems > cap) return hipErrorInvalidValue;
-    if (xdec_) ANX_TRY(hipFree(xdec_));
-    xdec_ = nullptr, xdec_cap_ = 0;
-    ANX_TRY(hipMalloc(reinterpret_cast<void**>(&xdec_), cap * sizeof(float)));
+    xdec_.reset();
+    xdec_cap_ = 0;
+    ANX_TRY(xdec_.try_alloc(cap));
     xdec_cap_ = cap;
   }
-  return hip::decode_u8(x, xdec_, elems, norm_, s);
+  return hip::decode_u8(x, xdec_.get(), elems, norm_, s);
 }
 
 hipError_t BlocksEngine::conv1_chunk(In xin, int n, const TilePlan& t, hipStream_t s, int c1_img0) {
   RoctxRange rx("anx conv1");
   const ConvSpec& k1 = b1_.conv;
-  const hip::OutView c1v{c1_ + static_cast<size_t>(c1_img0) * t.c1.size() * d_.W1 * d_.C1, t.c1.size(), d_.W1, d_.C1,
+  const hip::OutView c1v{c1_.get() + static_cast<size_t>(c1_img0) * t.c1.size() * d_.W1 * d_.C1, t.c1.size(), d_.W1, d_.C1,
                          0, 0, 0};
-  const bool wino = impl_ == Impl::Mfma && wv1_ != nullptr && use_winograd(k_.conv1_algo, n, t.c1.size(), full1_);
+  const bool wino = impl_ == Impl::Mfma && wv1_ && use_winograd(k_.conv1_algo, n, t.c1.size(), full1_);
   const float* xc = xin.f32;
   if (xin.u8 != nullptr) {
     if (wino && k_.conv1_u8 && norm_.C == 3) {
       const hip::Conv1WinoPlan w = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
       if (hip::conv1_wino_one_kernel(w, c1v, k_)) {  // where the float path launches conv1_fused: the byte form
-        ANX_TRY(hip::conv1_fused_u8(w, xin.u8, norm_, u1w_, b1d_, c1v, true, s));
+        ANX_TRY(hip::conv1_fused_u8(w, xin.u8, norm_, u1w_.get(), b1d_.get(), c1v, true, s));
         path_.conv1 = "fused";
         input_ = "u8_fused";
         return hipSuccess;
       }
     }
     ANX_TRY(decode_chunk(xin.u8, static_cast<size_t>(n) * t.in.size() * d_.W * d_.C0, s));
-    xc = xdec_;
+    xc = xdec_.get();
     input_ = "u8_decode";
   } else {
     input_ = "f32";
@@ -303,19 +254,19 @@ hipError_t BlocksEngine::conv1_chunk(In xin, int n, const TilePlan& t, hipStream
     const hip::Conv1WinoPlan w = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
     if (hip::conv1_wino_v_floats(w) > wv1_cap_) return hipErrorInvalidValue;
     bool one_kernel = false;  // set by the launcher where it picks the one-kernel form
-    ANX_TRY(hip::conv1_wino(w, xc, wv1_, u1w_, b1d_, c1v, true, s, k_, &one_kernel));
+    ANX_TRY(hip::conv1_wino(w, xc, wv1_.get(), u1w_.get(), b1d_.get(), c1v, true, s, k_, &one_kernel));
     path_.conv1 = one_kernel ? "fused" : "wino";
     return hipSuccess;
   }
   if (impl_ == Impl::Mfma) {
     const hip::ConvPlan p =
         hip::make_conv_plan(n, t.in.size(), d_.W, d_.C0, k1.K, k1.F, k1.S, k1.groups, k_.force_vec4, k_.force_scalar);
-    ANX_TRY(pack1(p));  // prepared by prepare() for the usual launches: a no-op then
+    ANX_TRY(pack(p1_, w1h_, p));  // prepared by prepare() for the usual launches: a no-op then
     path_.conv1 = "mfma";
-    return hip::conv2d_mfma(p, xc, w1p_, koff1_, b1d_, c1v, true, s);
+    return hip::conv2d_mfma(p, xc, p1_.w.get(), p1_.koff.get(), b1d_.get(), c1v, true, s);
   }
   path_.conv1 = "direct";
-  return hip::conv2d_direct(xc, w1_, b1d_, c1_, n, t.in.size(), d_.W, d_.C0, k1.K, k1.F, k1.S, 0, k1.groups, true,
+  return hip::conv2d_direct(xc, w1_.get(), b1d_.get(), c1_.get(), n, t.in.size(), d_.W, d_.C0, k1.K, k1.F, k1.S, 0, k1.groups, true,
                             s);
 }
 
@@ -340,8 +291,8 @@ hipError_t BlocksEngine::stage1_in(In x, int N, const TilePlan& t, hipStream_t s
     const int n = std::min(chunk, n_hi - n0);
     ANX_TRY(conv1_chunk(x.at(n0 * in_img), n, t, s));
     RoctxRange rx("anx pool1");
-    ANX_TRY(hip::maxpool(c1_, n, t.c1.size(), d_.W1, d_.C1, b1_.pool.F, b1_.pool.S,
-                         hip::OutView{q2_ + n0 * q_img, t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, b2_.conv.P, 0}, s));
+    ANX_TRY(hip::maxpool(c1_.get(), n, t.c1.size(), d_.W1, d_.C1, b1_.pool.F, b1_.pool.S,
+                         hip::OutView{q2_.get() + n0 * q_img, t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, b2_.conv.P, 0}, s));
     path_.pool1 = "kernel";
   }
   return hipSuccess;
@@ -351,21 +302,21 @@ hipError_t BlocksEngine::stage1_in(In x, int N, const TilePlan& t, hipStream_t s
 hipError_t BlocksEngine::conv2_chunk(int n, const TilePlan& t, const float* qc, float* yc, hipStream_t s) {
   RoctxRange rx("anx conv2+pool2+lrn");
   const ConvSpec& k2 = b2_.conv;
-  const hip::OutView c2v{c2_, t.c2.size(), d_.W2, d_.C2, 0, 0, 0};
-  if (impl_ == Impl::Mfma && wv_ != nullptr && use_winograd(k_.conv2_algo, n, t.c2.size(), full2_)) {
+  const hip::OutView c2v{c2_.get(), t.c2.size(), d_.W2, d_.C2, 0, 0, 0};
+  if (impl_ == Impl::Mfma && wv_ && use_winograd(k_.conv2_algo, n, t.c2.size(), full2_)) {
     const hip::WinoPlan w = hip::make_wino_plan(n, t.q.size(), wq_, d_.C1, k2.K, k2.groups, u2_m_);
     if (hip::wino_v_floats(w) > wv_cap_) return hipErrorInvalidValue;
-    ANX_TRY(hip::wino_input(w, qc, wv_, s));
-    ANX_TRY(hip::wino_conv2(w, wv_, u2w_, b2d_, c2v, true, s, k_));
+    ANX_TRY(hip::wino_input(w, qc, wv_.get(), s));
+    ANX_TRY(hip::wino_conv2(w, wv_.get(), u2w_.get(), b2d_.get(), c2v, true, s, k_));
     path_.conv2 = w.m == 4 ? "f45" : "f35";  // wino_conv2 launches by the plan's tile
   } else if (impl_ == Impl::Mfma) {
     const hip::ConvPlan p =
         hip::make_conv_plan(n, t.q.size(), wq_, d_.C1, k2.K, k2.F, k2.S, k2.groups, k_.force_vec4, k_.force_scalar);
-    ANX_TRY(pack2(p));
-    ANX_TRY(hip::conv2d_mfma(p, qc, w2p_, koff2_, b2d_, c2v, true, s));
+    ANX_TRY(pack(p2_, w2h_, p));
+    ANX_TRY(hip::conv2d_mfma(p, qc, p2_.w.get(), p2_.koff.get(), b2d_.get(), c2v, true, s));
     path_.conv2 = "mfma";
   } else {
-    ANX_TRY(hip::conv2d_direct(qc, w2_, b2d_, c2_, n, t.q.size(), wq_, d_.C1, k2.K, k2.F, k2.S, 0, k2.groups, true,
+    ANX_TRY(hip::conv2d_direct(qc, w2_.get(), b2d_.get(), c2_.get(), n, t.q.size(), wq_, d_.C1, k2.K, k2.F, k2.S, 0, k2.groups, true,
                                s));
     path_.conv2 = "direct";
   }
@@ -377,13 +328,13 @@ hipError_t BlocksEngine::pool2_chunk(int n, const TilePlan& t, float* yc, hipStr
   path_.pool2 = "kernel";  // every branch below pools the conv2 map with a kernel of its own
   if (b2_.has_lrn) {
     if (impl_ == Impl::Mfma)
-      return hip::maxpool_lrn(c2_, yc, n, t.c2.size(), d_.W2, d_.C2, b2_.pool.F, b2_.pool.S, l.N, l.alpha, l.beta,
+      return hip::maxpool_lrn(c2_.get(), yc, n, t.c2.size(), d_.W2, d_.C2, b2_.pool.F, b2_.pool.S, l.N, l.alpha, l.beta,
                               l.k, l.mode, s);
     // oracle path: separate pool and LRN kernels, staged through the conv1 workspace
-    ANX_TRY(hip::maxpool_direct(c2_, c1_, n, t.c2.size(), d_.W2, d_.C2, b2_.pool.F, b2_.pool.S, s));
-    return hip::lrn_direct(c1_, yc, n, t.out.size(), d_.Wp2, d_.C2, l.N, l.alpha, l.beta, l.k, l.mode, s);
+    ANX_TRY(hip::maxpool_direct(c2_.get(), c1_.get(), n, t.c2.size(), d_.W2, d_.C2, b2_.pool.F, b2_.pool.S, s));
+    return hip::lrn_direct(c1_.get(), yc, n, t.out.size(), d_.Wp2, d_.C2, l.N, l.alpha, l.beta, l.k, l.mode, s);
   }
-  return hip::maxpool(c2_, n, t.c2.size(), d_.W2, d_.C2, b2_.pool.F, b2_.pool.S,
+  return hip::maxpool(c2_.get(), n, t.c2.size(), d_.W2, d_.C2, b2_.pool.F, b2_.pool.S,
                       hip::OutView{yc, t.out.size(), d_.Wp2, d_.C2, 0, 0, 0}, s);
 }
 
@@ -396,13 +347,13 @@ hipError_t BlocksEngine::stage2(int N, const TilePlan& t, float* y, hipStream_t 
   const int chunk = k_.chunk2 > 0 ? std::min(chunk_, k_.chunk2) : chunk_;
   for (int n0 = n_lo; n0 < n_hi; n0 += chunk) {
     const int n = std::min(chunk, n_hi - n0);
-    ANX_TRY(conv2_chunk(n, t, q2_ + n0 * q_img, y + n0 * y_img, s));
+    ANX_TRY(conv2_chunk(n, t, q2_.get() + n0 * q_img, y + n0 * y_img, s));
   }
   return hipSuccess;
 }
 
 bool BlocksEngine::fused_pool1(int N, const TilePlan& t) const {
-  if (impl_ != Impl::Mfma || !k_.fuse_pool1 || wv_ == nullptr || d_.C1 % 32 || wq_ > 31) return false;
+  if (impl_ != Impl::Mfma || !k_.fuse_pool1 || !wv_ || d_.C1 % 32 || wq_ > 31) return false;
   // the fused kernel's pooling walk is 3x3 / stride 2 (pool_wino_in_kernel); other pool1 shapes take
   // the unfused maxpool + input transform
   if (b1_.pool.F != 3 || b1_.pool.S != 2) return false;
@@ -421,7 +372,7 @@ bool BlocksEngine::fused_pool1(int N, const TilePlan& t) const {
 }
 
 bool BlocksEngine::conv1_pools(int N, const TilePlan& t) const {
-  if (!k_.conv1_pool || k_.conv1_fused == 0 || k_.conv1_sub > 0 || wv1_ == nullptr || !fused_pool1(N, t)) return false;
+  if (!k_.conv1_pool || k_.conv1_fused == 0 || k_.conv1_sub > 0 || !wv1_ || !fused_pool1(N, t)) return false;
   // whole images: every output row, from the first conv1 / pool1 row on. The whole-image tile holds the
   // rows the output needs, not the map's last row where a pool drops it (an even H1 or Hp1): the kernels
   // take the tile's own row counts (t.c1.size() conv1 rows, t.p1.size() pool1 rows)
@@ -432,7 +383,7 @@ bool BlocksEngine::conv1_pools(int N, const TilePlan& t) const {
     const int n = std::min(chunk, N - n0);
     if (!use_winograd(k_.conv1_algo, n, t.c1.size(), full1_)) return false;
     const hip::Conv1WinoPlan w = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
-    const hip::OutView win{q2_, t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, b2_.conv.P, 0};
+    const hip::OutView win{q2_.get(), t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, b2_.conv.P, 0};
     if (w.H1 != t.c1.size() || !hip::conv1_fused_pool_eligible(w, win, t.p1.size(), d_.Wp1)) return false;
   }
   return true;
@@ -482,11 +433,11 @@ hipError_t BlocksEngine::tile_forward_in(In x, int N, const TilePlan& t, float* 
       const int m = std::min(s2, n - b0);
       const hip::WinoPlan w = hip::make_wino_plan(m, t.q.size(), wq_, d_.C1, k2.K, k2.groups, u2_m_);
       if (hip::wino_v_floats(w) > wv_cap_) return hipErrorInvalidValue;
-      ANX_TRY(hip::wino_pool_input(w, c1_ + b0 * c1_img, t.c1.size(), d_.W1, t.q.lo, d_.Hp1, d_.Wp1, k2.P, t.c1.lo,
-                                   wv_, s, b1_.pool.F, b1_.pool.S));
+      ANX_TRY(hip::wino_pool_input(w, c1_.get() + b0 * c1_img, t.c1.size(), d_.W1, t.q.lo, d_.Hp1, d_.Wp1, k2.P, t.c1.lo,
+                                   wv_.get(), s, b1_.pool.F, b1_.pool.S));
       path_.pool1 = "input_transform";
-      const hip::OutView c2v{c2_ + b0 * c2_img, t.c2.size(), d_.W2, d_.C2, 0, 0, 0};
-      ANX_TRY(hip::wino_conv2(w, wv_, u2w_, b2d_, c2v, true, s, k_));
+      const hip::OutView c2v{c2_.get() + b0 * c2_img, t.c2.size(), d_.W2, d_.C2, 0, 0, 0};
+      ANX_TRY(hip::wino_conv2(w, wv_.get(), u2w_.get(), b2d_.get(), c2v, true, s, k_));
       path_.conv2 = w.m == 4 ? "f45" : "f35";
     }
     ANX_TRY(pool2_chunk(n, t, y + n0 * y_img, s));
@@ -512,18 +463,18 @@ hipError_t BlocksEngine::tile_forward_conv1_pool(In x, int N, const TilePlan& t,
     {
       RoctxRange rx("anx conv1+pool1");
       const hip::Conv1WinoPlan w1 = hip::make_conv1_wino_plan(n, t.in.size(), d_.W, k1.K, k1.F);
-      const hip::OutView win{q2_ + n0 * q_img, t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, k2.P, 0};
+      const hip::OutView win{q2_.get() + n0 * q_img, t.q.size(), wq_, d_.C1, t.p1.lo - t.q.lo, k2.P, 0};
       const In xc = x.at(n0 * in_img);
       if (xc.u8 != nullptr && k_.conv1_u8 && norm_.C == 3) {
-        ANX_TRY(hip::conv1_fused_pool_u8(w1, xc.u8, norm_, u1w_, b1d_, win, c1_, hp1, d_.Wp1, true, s, k_.conv1_fused - 1));
+        ANX_TRY(hip::conv1_fused_pool_u8(w1, xc.u8, norm_, u1w_.get(), b1d_.get(), win, c1_.get(), hp1, d_.Wp1, true, s, k_.conv1_fused - 1));
         input_ = "u8_fused";
       } else {
         const float* xf = xc.f32;
         if (xc.u8 != nullptr) {
           ANX_TRY(decode_chunk(xc.u8, static_cast<size_t>(n) * in_img, s));
-          xf = xdec_;
+          xf = xdec_.get();
         }
-        ANX_TRY(hip::conv1_fused_pool(w1, xf, u1w_, b1d_, win, c1_, hp1, d_.Wp1, true, s, k_.conv1_fused - 1));
+        ANX_TRY(hip::conv1_fused_pool(w1, xf, u1w_.get(), b1d_.get(), win, c1_.get(), hp1, d_.Wp1, true, s, k_.conv1_fused - 1));
         input_ = xc.u8 != nullptr ? "u8_decode" : "f32";
       }
       path_.conv1 = "fused_pool";
@@ -536,30 +487,30 @@ hipError_t BlocksEngine::tile_forward_conv1_pool(In x, int N, const TilePlan& t,
     // behind it (2 x 13 x 13 < 27 x 27 pixels per image: inside the conv2 map's workspace)
     const bool pool2 = conv2_pools(t);
     const size_t pimg = static_cast<size_t>(d_.Hp2) * d_.Wp2 * d_.C2;
-    float* const p2 = c2_ + static_cast<size_t>(n) * pimg;
+    float* const p2 = c2_.get() + static_cast<size_t>(n) * pimg;
     int ty2 = 0, tx2 = 0;
     for (int b0 = 0; b0 < n; b0 += s2) {
       const int m = std::min(s2, n - b0);
       const hip::WinoPlan w = hip::make_wino_plan(m, t.q.size(), wq_, d_.C1, k2.K, k2.groups, u2_m_);
       if (hip::wino_v_floats(w) > wv_cap_) return hipErrorInvalidValue;
-      ANX_TRY(hip::wino_window_merge_input(w, q2_ + (n0 + b0) * q_img, c1_ + b0 * p1_img, b0, w1.ty, w1.tx, t.q.lo,
-                                           hp1, d_.Wp1, k2.P, wv_, s, u2_m_ == 4 ? k_.conv2_in_pg : 32));
+      ANX_TRY(hip::wino_window_merge_input(w, q2_.get() + (n0 + b0) * q_img, c1_.get() + b0 * p1_img, b0, w1.ty, w1.tx, t.q.lo,
+                                           hp1, d_.Wp1, k2.P, wv_.get(), s, u2_m_ == 4 ? k_.conv2_in_pg : 32));
       if (pool2) {
         ty2 = w.ty;
         tx2 = w.tx;
-        ANX_TRY(hip::wino_gemm_conv2_f45_pool(wv_, u2w_, b2d_, c2_ + b0 * pimg, p2 + b0 * pimg, w.P, w.ty, w.tx, w.Ho,
+        ANX_TRY(hip::wino_gemm_conv2_f45_pool(wv_.get(), u2w_.get(), b2d_.get(), c2_.get() + b0 * pimg, p2 + b0 * pimg, w.P, w.ty, w.tx, w.Ho,
                                               w.Wo, d_.Hp2, d_.Wp2, w.K, true, s, k_.conv2_occ,
                                               k_.conv2_sched != 0));
         path_.conv2 = "f45";
       } else {
-        const hip::OutView c2v{c2_ + b0 * c2_img, t.c2.size(), d_.W2, d_.C2, 0, 0, 0};
-        ANX_TRY(hip::wino_conv2(w, wv_, u2w_, b2d_, c2v, true, s, k_));
+        const hip::OutView c2v{c2_.get() + b0 * c2_img, t.c2.size(), d_.W2, d_.C2, 0, 0, 0};
+        ANX_TRY(hip::wino_conv2(w, wv_.get(), u2w_.get(), b2d_.get(), c2v, true, s, k_));
         path_.conv2 = w.m == 4 ? "f45" : "f35";
       }
     }
     if (pool2) {
       const LrnSpec& l = b2_.lrn;
-      ANX_TRY(hip::lrn_pooled_merge(c2_, p2, y + n0 * y_img, n, d_.Hp2, d_.Wp2, d_.C2, ty2, tx2, s2, l.N, l.alpha, l.beta,
+      ANX_TRY(hip::lrn_pooled_merge(c2_.get(), p2, y + n0 * y_img, n, d_.Hp2, d_.Wp2, d_.C2, ty2, tx2, s2, l.N, l.alpha, l.beta,
                                     l.k, l.mode, s, k_.lrn_wgs));
       path_.pool2 = "gemm_epilogue";
     } else {

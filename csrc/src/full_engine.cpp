@@ -9,27 +9,19 @@
 #include "anx/bf16_ops.hpp"
 #include "anx/upload.hpp"
 
-#define ANX_TRY(expr)                \
-  do {                               \
-    hipError_t _e = (expr);          \
-    if (_e != hipSuccess) return _e; \
-  } while (0)
-
 namespace anx {
 
 namespace {
-void check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-void* dalloc(size_t bytes) {
-  void* p = nullptr;
-  check(hipMalloc(&p, std::max<size_t>(bytes, 16)), "hipMalloc");
-  return p;
-}
 // C, K, F, S per layer (groups filled in per instance for conv2)
 constexpr int kGeom[8][4] = {{3, 96, 11, 4},      {96, 256, 5, 1},    {256, 384, 3, 1},   {384, 384, 3, 1},
                              {384, 256, 3, 1},    {9216, 4096, 1, 1}, {4096, 4096, 1, 1}, {4096, 0, 1, 1}};
 }  // namespace
+
+// xb_ holds the raw image as bf16 (taps8) or its polyphase form [57,57,48], the larger and the one tap() reports
+const FullEngine::ActSpec FullEngine::kActs[FullEngine::kNumActs] = {
+    {55 * 55 * 96, false},  {31 * 31 * 96, true},   {27 * 27 * 256, false}, {15 * 15 * 256, true},
+    {15 * 15 * 384, true},  {15 * 15 * 384, true},  {13 * 13 * 256, false}, {9216, false},
+    {4096, false},          {4096, false},          {std::max(227 * 227 * 3, 57 * 57 * 48), false}};
 
 void full_weight_shapes(int classes, int groups2, size_t wn[8], size_t bn[8]) {
   for (int i = 0; i < 8; ++i) {
@@ -54,8 +46,7 @@ FullEngine::FullEngine(const FullWeights& w, int classes, int max_batch, int gro
     L.S = kGeom[i][3];
     L.groups = i == 1 ? groups2 : 1;
     L.host = w.w[i];
-    L.bias = static_cast<float*>(dalloc(bn[i] * 4));
-    check(upload_h2d(L.bias, w.b[i].data(), bn[i] * 4), "H2D bias");
+    L.bias = DevBuf<float>::upload(w.b[i], 16);
   }
   // Conv1 polyphase (the fp32 Winograd Conv1's rewrite, conv1_wino.hip): space-to-depth by the stride
   // turns 11x11/4 over 3 channels into 3x3/1 over 48, so the implicit GEMM's A gathers are aligned
@@ -85,32 +76,19 @@ FullEngine::FullEngine(const FullWeights& w, int classes, int max_batch, int gro
     L.S = 1;
     std::vector<uint16_t> rp;
     hip::pack_conv1_ring_weights(L.host.data(), rp);
-    w1ring_ = dalloc(rp.size() * 2);
-    check(upload_h2d(w1ring_, rp.data(), rp.size() * 2), "H2D conv1 ring weights");
+    w1ring_ = DevBuf<uint16_t>::upload(rp, 16);
   }
   {
     int dev = 0;
-    check(hipGetDevice(&dev), "hipGetDevice");
-    check(hipDeviceGetAttribute(&cus_, hipDeviceAttributeMultiprocessorCount, dev), "CU count");
+    hip_check(hipGetDevice(&dev), "hipGetDevice");
+    hip_check(hipDeviceGetAttribute(&cus_, hipDeviceAttributeMultiprocessorCount, dev), "CU count");
   }
   chunk_ = std::max(1, std::min(max_batch, static_cast<int>(((1UL << 31) - 1) / (55UL * 55 * 96))));
   const size_t n = static_cast<size_t>(chunk_);
-  xb_ = dalloc(n * std::max(227 * 227 * 3, 57 * 57 * 48) * 2);
-  c1_ = dalloc(n * 55 * 55 * 96 * 2);
-  q2_ = dalloc(n * 31 * 31 * 96 * 2);
-  c2_ = dalloc(n * 27 * 27 * 256 * 2);
-  q3_ = dalloc(n * 15 * 15 * 256 * 2);
-  q4_ = dalloc(n * 15 * 15 * 384 * 2);
-  q5_ = dalloc(n * 15 * 15 * 384 * 2);
-  c5_ = dalloc(n * 13 * 13 * 256 * 2);
-  f6_ = dalloc(n * 9216 * 2);
-  f7_ = dalloc(n * 4096 * 2);
-  f8_ = dalloc(n * 4096 * 2);
+  for (int i = 0; i < kNumActs; ++i) act_[i] = DevBuf<uint16_t>(n * kActs[i].elems, 16);
   // zero borders of the padded windows once; kernels only ever write the interiors
-  check(hipMemset(q2_, 0, n * 31 * 31 * 96 * 2), "memset");
-  check(hipMemset(q3_, 0, n * 15 * 15 * 256 * 2), "memset");
-  check(hipMemset(q4_, 0, n * 15 * 15 * 384 * 2), "memset");
-  check(hipMemset(q5_, 0, n * 15 * 15 * 384 * 2), "memset");
+  for (int i = 0; i < kNumActs; ++i)
+    if (kActs[i].window) hip_check(hipMemset(act_[i].get(), 0, n * kActs[i].elems * 2), "memset");
   size_t ws = 0;  // largest split-K slab set over the FC layers and every batch the engine can see
   for (int i = 5; i < 8; ++i)
     for (int b = 1; b <= chunk_; ++b) {
@@ -122,17 +100,7 @@ FullEngine::FullEngine(const FullWeights& w, int classes, int max_batch, int gro
         if (f.cfg >= 0) ws = std::max(ws, static_cast<size_t>(f.ksplit) * b * L_[i].K);
       }
     }
-  if (ws) ws_ = static_cast<float*>(dalloc(ws * 4));
-}
-
-FullEngine::~FullEngine() {
-  if (mark_) (void)hipEventDestroy(mark_);
-  for (Layer& L : L_)
-    for (void* p : {L.wp, static_cast<void*>(L.koff), static_cast<void*>(L.bias)})
-      if (p) (void)hipFree(p);
-  for (void* p : {xb_, c1_, q2_, c2_, q3_, q4_, q5_, c5_, f6_, f7_, f8_, static_cast<void*>(ws_), w1ring_,
-                  static_cast<void*>(xdec_)})
-    if (p) (void)hipFree(p);
+  if (ws) ws_ = DevBuf<float>(ws, 16);
 }
 
 hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip::OutViewB out, float* out_f32,
@@ -143,12 +111,15 @@ hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip:
     std::vector<uint16_t> pk;
     std::vector<int> ko;
     hip::pack_conv_weights_bf16(p, L.host.data(), pk, ko);
-    if (L.wp) ANX_TRY(hipFree(L.wp));
-    if (L.koff) ANX_TRY(hipFree(L.koff));
-    ANX_TRY(hipMalloc(&L.wp, pk.size() * 2));
-    ANX_TRY(hipMalloc(&L.koff, ko.size() * 4));
-    ANX_TRY(upload_h2d(L.wp, pk.data(), pk.size() * 2));
-    ANX_TRY(upload_h2d(L.koff, ko.data(), ko.size() * 4));
+    // both new buffers first, then commit them with the key: a failure leaves the layer as it was
+    DevBuf<uint16_t> wp;
+    DevBuf<int> koff;
+    ANX_TRY(wp.try_alloc(pk.size()));
+    ANX_TRY(koff.try_alloc(ko.size()));
+    ANX_TRY(upload_h2d(wp.get(), pk.data(), pk.size() * 2));
+    ANX_TRY(upload_h2d(koff.get(), ko.data(), ko.size() * 4));
+    L.wp = std::move(wp);
+    L.koff = std::move(koff);
     L.key = p.variant;
   }
   const bool fc = p.Hp == 1 && p.Wp == 1 && p.F == 1;
@@ -167,27 +138,27 @@ hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip:
   };
   if (fc && k_.bf16_big != -2) {  // wide-tile FC: one 256-row tile of the batch, K split over the CUs
     hip::BigFc f = hip::pick_bf16_big_fc(p, cus_, k_.bf16_fc_cfg, k_.bf16_fc_minkt);
-    if (f.cfg >= 0 && k_.bf16_big >= 0 && hip::conv_bf16_big_ok(p, k_.bf16_big, hip::OutViewB{B(ws_), 1, 1, p.Kg, 0, 0, 0}))
+    if (f.cfg >= 0 && k_.bf16_big >= 0 && hip::conv_bf16_big_ok(p, k_.bf16_big, hip::OutViewB{B(ws_.get()), 1, 1, p.Kg, 0, 0, 0}))
       f.cfg = k_.bf16_big;
     if (f.cfg >= 0 && (f.ksplit > 1 || out_f32)) {
-      ANX_TRY(hip::conv2d_bf16_big(p, f.cfg, x, L.wp, L.koff, L.bias, hip::OutViewB{B(ws_), 1, 1, p.Kg, 0, 0, 0}, relu,
-                                   s, hip::SplitK{f.ksplit, ws_}, big(f.ksplit)));
-      return hip::splitk_reduce_bf16(ws_, f.ksplit, N, L.K, L.bias, relu, out, out_f32, s);
+      ANX_TRY(hip::conv2d_bf16_big(p, f.cfg, x, L.wp.get(), L.koff.get(), L.bias.get(), hip::OutViewB{B(ws_.get()), 1, 1, p.Kg, 0, 0, 0}, relu,
+                                   s, hip::SplitK{f.ksplit, ws_.get()}, big(f.ksplit)));
+      return hip::splitk_reduce_bf16(ws_.get(), f.ksplit, N, L.K, L.bias.get(), relu, out, out_f32, s);
     }
-    if (f.cfg >= 0) return hip::conv2d_bf16_big(p, f.cfg, x, L.wp, L.koff, L.bias, out, relu, s, {}, big(1));
+    if (f.cfg >= 0) return hip::conv2d_bf16_big(p, f.cfg, x, L.wp.get(), L.koff.get(), L.bias.get(), out, relu, s, {}, big(1));
   }
   const int ks = hip::fc_split_k(p);
   if (ks > 1) {  // FC layer at a small batch: K split over ~one workgroup per CU, then a reduce
-    ANX_TRY(tile(ks, hip::conv2d_bf16(p, x, L.wp, L.koff, L.bias, out, out_f32, relu, s, hip::SplitK{ks, ws_},
+    ANX_TRY(tile(ks, hip::conv2d_bf16(p, x, L.wp.get(), L.koff.get(), L.bias.get(), out, out_f32, relu, s, hip::SplitK{ks, ws_.get()},
                                       k_.bf16_glds, &rec.id)));
-    return hip::splitk_reduce_bf16(ws_, ks, N, L.K, L.bias, relu, out, out_f32, s);
+    return hip::splitk_reduce_bf16(ws_.get(), ks, N, L.K, L.bias.get(), relu, out, out_f32, s);
   }
   if (!fc && !out_f32 && k_.bf16_big != -2) {  // wide-tile kernel: forced config if it applies, else the cost model
     const int cfg = k_.bf16_big >= 0 && hip::conv_bf16_big_ok(p, k_.bf16_big, out) ? k_.bf16_big
                                                                                     : hip::pick_bf16_big_cfg(p, out, cus_);
-    if (cfg >= 0) return hip::conv2d_bf16_big(p, cfg, x, L.wp, L.koff, L.bias, out, relu, s, {}, big(1));
+    if (cfg >= 0) return hip::conv2d_bf16_big(p, cfg, x, L.wp.get(), L.koff.get(), L.bias.get(), out, relu, s, {}, big(1));
   }
-  return tile(1, hip::conv2d_bf16(p, x, L.wp, L.koff, L.bias, out, out_f32, relu, s, {}, k_.bf16_glds, &rec.id));
+  return tile(1, hip::conv2d_bf16(p, x, L.wp.get(), L.koff.get(), L.bias.get(), out, out_f32, relu, s, {}, k_.bf16_glds, &rec.id));
 }
 
 hipError_t FullEngine::forward(const float* x, int N, float* logits, hipStream_t s, bool mark) {
@@ -203,10 +174,13 @@ void FullEngine::set_input_norm(const float* scale, const float* offset) {
 }
 
 hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* logits, hipStream_t s, bool mark) {
-  if (mark && !mark_) ANX_TRY(hipEventCreateWithFlags(&mark_, hipEventDisableTiming));
+  if (mark && !mark_) ANX_TRY(mark_.try_create(hipEventDisableTiming));
   using hip::OutViewB;
   auto B = [](void* p) { return static_cast<__bf16*>(p); };
   constexpr size_t kImage = 227 * 227 * 3;
+  void *const xb_ = a(kXb), *const c1_ = a(kC1), *const q2_ = a(kQ2), *const c2_ = a(kC2), *const q3_ = a(kQ3),
+             *const q4_ = a(kQ4), *const q5_ = a(kQ5), *const c5_ = a(kC5), *const f6_ = a(kF6), *const f7_ = a(kF7),
+             *const f8_ = a(kF8);
   // bytes straight into the row-band kernel, else decoded into the workspace first
   const bool u8_ring = xu && poly1_ && k_.bf16_conv1 == 2 && k_.bf16_u8 != 0;
   if (xu && !u8_ring && !xdec_) {
@@ -214,12 +188,12 @@ hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* log
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
       return hipErrorStreamCaptureUnsupported;
-    ANX_TRY(hipMalloc(reinterpret_cast<void**>(&xdec_), static_cast<size_t>(chunk_) * kImage * sizeof(float)));
+    ANX_TRY(xdec_.try_alloc(static_cast<size_t>(chunk_) * kImage));
   }
   for (int n0 = 0; n0 < N; n0 += chunk_) {
     const int n = std::min(chunk_, N - n0);
-    const float* xn = xf ? xf + static_cast<size_t>(n0) * kImage : xdec_;
-    if (xu && !u8_ring) ANX_TRY(hip::decode_u8(xu + static_cast<size_t>(n0) * kImage, xdec_, n * kImage, norm_, s));
+    const float* xn = xf ? xf + static_cast<size_t>(n0) * kImage : xdec_.get();
+    if (xu && !u8_ring) ANX_TRY(hip::decode_u8(xu + static_cast<size_t>(n0) * kImage, xdec_.get(), n * kImage, norm_, s));
     input_ = !xu ? "f32" : u8_ring ? "u8_ring" : "u8_decode";
     bool pooled = false;  // pool1 done with Conv1
     if (poly1_) {
@@ -228,10 +202,10 @@ hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* log
         const OutViewB c1v{B(c1_), 55, 55, 96, 0, 0, 0};
         hip::RingRan ran;
         if (u8_ring)
-          ANX_TRY(hip::conv1_bf16_ring_u8(xu + static_cast<size_t>(n0) * kImage, norm_, n, w1ring_, L_[0].bias, c1v, true,
+          ANX_TRY(hip::conv1_bf16_ring_u8(xu + static_cast<size_t>(n0) * kImage, norm_, n, w1ring_.get(), L_[0].bias.get(), c1v, true,
                                           s, cus_, k_.bf16_pool1 ? &q2v : nullptr, &ran));
         else
-          ANX_TRY(hip::conv1_bf16_ring(xn, n, w1ring_, L_[0].bias, c1v, true, s, cus_, true,
+          ANX_TRY(hip::conv1_bf16_ring(xn, n, w1ring_.get(), L_[0].bias.get(), c1v, true, s, cus_, true,
                                        k_.bf16_pool1 ? &q2v : nullptr, &ran));
         pooled = k_.bf16_pool1 != 0;
         path_.conv1 = u8_ring ? (ran.pool ? "ring_u8_pool" : "ring_u8") : (ran.pool ? "ring_f32_pool" : "ring_f32");
@@ -240,7 +214,7 @@ hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* log
         ANX_TRY(hip::f32_to_bf16_s2d4(xn, xb_, n, 227, 227, s));
         if (k_.bf16_conv1 == 1) {
           hip::RingRan ran;
-          ANX_TRY(hip::conv1_bf16_ring(xb_, n, w1ring_, L_[0].bias, OutViewB{B(c1_), 55, 55, 96, 0, 0, 0}, true, s, cus_,
+          ANX_TRY(hip::conv1_bf16_ring(xb_, n, w1ring_.get(), L_[0].bias.get(), OutViewB{B(c1_), 55, 55, 96, 0, 0, 0}, true, s, cus_,
                                        false, nullptr, &ran));
           path_.conv1 = "ring";
           path_.conv1_segs = ran.segs;
@@ -260,7 +234,7 @@ hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* log
     ANX_TRY(conv(L_[1], n, 31, 31, q2_, OutViewB{B(c2_), 27, 27, 256, 0, 0, 0}, nullptr, true, s));
     ANX_TRY(hip::maxpool_lrn_bf16(c2_, n, 27, 27, 256, 3, 2, 5, 1e-4f, 0.75f, 2.0f, lrn_,
                                   OutViewB{B(q3_), 15, 15, 256, 1, 1, 0}, s, k_.bf16_lrn_tile));
-    if (mark && n0 == 0) ANX_TRY(hipEventRecord(mark_, s));
+    if (mark && n0 == 0) ANX_TRY(hipEventRecord(mark_.get(), s));
     ANX_TRY(conv(L_[2], n, 15, 15, q3_, OutViewB{B(q4_), 15, 15, 384, 1, 1, 0}, nullptr, true, s));
     ANX_TRY(conv(L_[3], n, 15, 15, q4_, OutViewB{B(q5_), 15, 15, 384, 1, 1, 0}, nullptr, true, s));
     ANX_TRY(conv(L_[4], n, 15, 15, q5_, OutViewB{B(c5_), 13, 13, 256, 0, 0, 0}, nullptr, true, s));
@@ -274,13 +248,9 @@ hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* log
 }
 
 size_t FullEngine::tap(int i, int N, void* dst, hipStream_t s) const {
-  static const size_t kElems[11] = {55 * 55 * 96,   31 * 31 * 96, 27 * 27 * 256, 15 * 15 * 256,
-                                    15 * 15 * 384,  15 * 15 * 384, 13 * 13 * 256, 9216,
-                                    4096,           4096,          57 * 57 * 48};
-  void* const bufs[11] = {c1_, q2_, c2_, q3_, q4_, q5_, c5_, f6_, f7_, f8_, xb_};
-  if (i < 0 || i >= 11 || (i == 10 && !poly1_) || N < 1 || N > chunk_) return 0;
-  if (hipMemcpyAsync(dst, bufs[i], kElems[i] * N * 2, hipMemcpyDeviceToDevice, s) != hipSuccess) return 0;
-  return kElems[i];
+  if (i < 0 || i >= kNumActs || (i == kXb && !poly1_) || N < 1 || N > chunk_) return 0;
+  if (hipMemcpyAsync(dst, act_[i].get(), kActs[i].elems * N * 2, hipMemcpyDeviceToDevice, s) != hipSuccess) return 0;
+  return kActs[i].elems;
 }
 
 }  // namespace anx

@@ -16,12 +16,11 @@
 #include <string>
 #include <utility>
 
+#include "anx/device.hpp"
+
 namespace anx {
 
 namespace {
-void hip_ok(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
 const char* kBufName[] = {"X", "Tile", "Win", "Y", "YFull"};
 constexpr int kB = static_cast<int>(BufId::kCount);
 }  // namespace
@@ -109,7 +108,7 @@ struct DeviceBase : Transport {
       for (int b = 0; b < kB; ++b) buf_[p][b] = bufs[p][b];
   }
   void copy2d(char* dst, size_t dpitch, const char* src, size_t spitch, size_t w, size_t h, hipStream_t s) {
-    hip_ok(hipMemcpy2DAsync(dst, dpitch, src, spitch, w, h, hipMemcpyDeviceToDevice, s), "hipMemcpy2DAsync");
+    hip_check(hipMemcpy2DAsync(dst, dpitch, src, spitch, w, h, hipMemcpyDeviceToDevice, s), "hipMemcpy2DAsync");
   }
   // src == dst transfers (the root's own scatter / gather share) on the given stream; none when the
   // runtime aliased the two buffers (the root's whole-image tiles live inside X / YFull)
@@ -142,7 +141,7 @@ struct RcclTransport : DeviceBase {
   bool loopback_ = false, chain_ = true;
   std::unique_ptr<DeviceComm> dc_[2];
   DeviceComm* last_ = nullptr;  // communicator of the previous phase
-  std::map<std::tuple<int, int, int>, void*> stage_;  // (phase, chunk, transfer) -> contiguous staging
+  std::map<std::tuple<int, int, int>, DevBuf<char>> stage_;  // (phase, chunk, transfer) -> contiguous staging
   RcclTransport(HostComm* c, int device, int rank, bool loopback) : hc_(c), device_(device), loopback_(loopback) {
     rank_ = rank;
     const char* e = std::getenv("ANX_V5_COMM_ORDER");
@@ -164,7 +163,7 @@ struct RcclTransport : DeviceBase {
     if (!live()) return;
     connect();
     dc_[0]->bcast(buf, bytes, root);
-    hip_ok(hipStreamSynchronize(dc_[0]->stream()), "hipStreamSynchronize");
+    hip_check(hipStreamSynchronize(dc_[0]->stream()), "hipStreamSynchronize");
   }
   void bind(const Schedule& s, void* const bufs[2][kB], hipStream_t) override {
     bind_bufs(bufs);
@@ -173,9 +172,9 @@ struct RcclTransport : DeviceBase {
     if (!s.phase[static_cast<int>(Phase::P1Halo)].empty()) dc_[1] = make_comm();
   }
   void* staging(Phase ph, const Transfer& x, size_t i) {
-    void*& p = stage_[{static_cast<int>(ph), x.chunk, x.seq >= 0 ? x.seq : static_cast<int>(i)}];
-    if (!p) hip_ok(hipMalloc(&p, x.bytes()), "hipMalloc staging");
-    return p;
+    DevBuf<char>& b = stage_[{static_cast<int>(ph), x.chunk, x.seq >= 0 ? x.seq : static_cast<int>(i)}];
+    if (!b) b = DevBuf<char>(x.bytes(), 0);
+    return b.get();
   }
   void run_phase(Phase ph, const std::vector<Transfer>& xs, hipStream_t compute, int par) override {
     local(xs, compute, par);
@@ -217,7 +216,6 @@ struct RcclTransport : DeviceBase {
     dc->before(compute);
   }
   void close() override {
-    for (auto& kv : stage_) (void)hipFree(kv.second);
     stage_.clear();
     last_ = nullptr;
     dc_[1].reset();
@@ -250,14 +248,14 @@ struct PeerTransport : DeviceBase {
   bool flags_ = true;
   int np_ = 1;
   std::vector<std::array<void*, kB * 2>> peer_buf_;  // mapped Tile / YFull of every rank
-  std::map<std::pair<int, int>, void*> slot_;        // own halo slots: (transfer, parity)
+  std::map<std::pair<int, int>, DevBuf<char>> slot_;  // own halo slots: (transfer, parity)
   std::map<std::pair<int, int>, void*> peer_slot_;   // receivers' slots this rank pushes into
   // flags mode
-  uint32_t* flags_mine_ = nullptr;  // [np][kCh], written by the senders
+  DevBuf<uint32_t> flags_mine_;      // [np][kCh], written by the senders
   std::vector<uint32_t*> flags_of_;  // every rank's flag array, mapped
   std::vector<std::array<uint32_t, kCh>> sent_seq_, recv_seq_;
   // notes mode
-  hipEvent_t sent_[kCh][2] = {};
+  HipEvent sent_[kCh][2];
   std::vector<std::array<std::array<hipEvent_t, 2>, kCh>> peer_sent_;
   std::vector<void*> opened_;
   std::vector<hipEvent_t> opened_ev_;
@@ -286,23 +284,23 @@ struct PeerTransport : DeviceBase {
   void* share(void* mine, int r) {  // collective: rank r's allocation mapped here
     hipIpcMemHandle_t h{};
     int flag = mine ? 1 : 0;
-    if (r == rank_ && mine) hip_ok(hipIpcGetMemHandle(&h, mine), "hipIpcGetMemHandle");
+    if (r == rank_ && mine) hip_check(hipIpcGetMemHandle(&h, mine), "hipIpcGetMemHandle");
     c_->bcast(&flag, sizeof flag, r);
     if (!flag) return nullptr;
     c_->bcast(&h, sizeof h, r);
     if (r == rank_) return mine;
     void* p = nullptr;
-    hip_ok(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle");
+    hip_check(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle");
     opened_.push_back(p);
     return p;
   }
   hipEvent_t share_ev(hipEvent_t mine, int r) {
     hipIpcEventHandle_t h{};
-    if (r == rank_) hip_ok(hipIpcGetEventHandle(&h, mine), "hipIpcGetEventHandle");
+    if (r == rank_) hip_check(hipIpcGetEventHandle(&h, mine), "hipIpcGetEventHandle");
     c_->bcast(&h, sizeof h, r);
     if (r == rank_) return mine;
     hipEvent_t e = nullptr;
-    hip_ok(hipIpcOpenEventHandle(&e, h), "hipIpcOpenEventHandle");
+    hip_check(hipIpcOpenEventHandle(&e, h), "hipIpcOpenEventHandle");
     opened_ev_.push_back(e);
     return e;
   }
@@ -312,23 +310,23 @@ struct PeerTransport : DeviceBase {
     if (connected_ || record_only) return;
     connected_ = true;
     np_ = c_->size();
-    hip_ok(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
     if (flags_) {
       int can = 0;
       if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device_) != hipSuccess || !can)
         throw std::runtime_error("peer transport: device lacks hipStreamWaitValue32 (set ANX_PEER_SYNC=notes)");
       const size_t bytes = static_cast<size_t>(np_) * kCh * sizeof(uint32_t);
-      hip_ok(hipMalloc(reinterpret_cast<void**>(&flags_mine_), bytes), "hipMalloc flags");
-      hip_ok(hipMemset(flags_mine_, 0, bytes), "hipMemset flags");
-      hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
+      flags_mine_ = DevBuf<uint32_t>(static_cast<size_t>(np_) * kCh);
+      hip_check(hipMemset(flags_mine_.get(), 0, bytes), "hipMemset flags");
+      hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
       flags_of_.assign(np_, nullptr);
-      for (int r = 0; r < np_; ++r) flags_of_[r] = static_cast<uint32_t*>(share(r == rank_ ? flags_mine_ : nullptr, r));
+      for (int r = 0; r < np_; ++r) flags_of_[r] = static_cast<uint32_t*>(share(r == rank_ ? flags_mine_.get() : nullptr, r));
       sent_seq_.assign(np_, {});
       recv_seq_.assign(np_, {});
     } else {
       for (auto& ch : sent_)
         for (auto& e : ch)
-          hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventInterprocess), "hipEventCreate IPC");
+          e = HipEvent::create(hipEventDisableTiming | hipEventInterprocess, "hipEventCreate IPC");
       peer_sent_.assign(np_, {});
       for (int r = 0; r < np_; ++r)
         for (int ch = 0; ch < kCh; ++ch)
@@ -340,10 +338,10 @@ struct PeerTransport : DeviceBase {
     if (record_only || !c_ || c_->size() == 1) return;
     connect();
     void* src = share(rank_ == root ? buf : nullptr, root);
-    if (rank_ != root) hip_ok(hipMemcpy(buf, src, bytes, hipMemcpyDeviceToDevice), "hipMemcpy bcast");
+    if (rank_ != root) hip_check(hipMemcpy(buf, src, bytes, hipMemcpyDeviceToDevice), "hipMemcpy bcast");
     c_->barrier();  // every rank copied: unmap the root's buffer
     if (rank_ != root) {
-      hip_ok(hipIpcCloseMemHandle(src), "hipIpcCloseMemHandle");
+      hip_check(hipIpcCloseMemHandle(src), "hipIpcCloseMemHandle");
       opened_.pop_back();
     }
   }
@@ -362,8 +360,9 @@ struct PeerTransport : DeviceBase {
       for (int p = 0; p < 2; ++p) {
         void* mine = nullptr;
         if (hs[i].dst == rank_) {
-          hip_ok(hipMalloc(&mine, hs[i].bytes()), "hipMalloc halo slot");
-          slot_[{static_cast<int>(i), p}] = mine;
+          DevBuf<char>& own = slot_[{static_cast<int>(i), p}];
+          own = DevBuf<char>(hs[i].bytes(), 0);
+          mine = own.get();
         }
         void* m = share(mine, hs[i].dst);
         if (hs[i].src == rank_) peer_slot_[{static_cast<int>(i), p}] = m;
@@ -389,10 +388,10 @@ struct PeerTransport : DeviceBase {
     if (!to.empty()) {
       if (flags_) {
         for (int d : to)
-          hip_ok(hipStreamWriteValue32(s, flags_of_[d] + rank_ * kCh + ch, ++sent_seq_[d][ch], 0),
+          hip_check(hipStreamWriteValue32(s, flags_of_[d] + rank_ * kCh + ch, ++sent_seq_[d][ch], 0),
                  "hipStreamWriteValue32");
       } else {
-        hip_ok(hipEventRecord(sent_[ch][par], s), "hipEventRecord IPC");
+        hip_check(hipEventRecord(sent_[ch][par], s), "hipEventRecord IPC");
         const int msg = ch * 2 + par;
         for (int d : to) c_->isend(&msg, sizeof msg, d);
         c_->wait_all();
@@ -407,19 +406,19 @@ struct PeerTransport : DeviceBase {
       if (std::find(from.begin(), from.end(), x.src) == from.end()) {
         from.push_back(x.src);
         if (flags_) {
-          hip_ok(hipStreamWaitValue32(s, flags_mine_ + x.src * kCh + ch, ++recv_seq_[x.src][ch],
+          hip_check(hipStreamWaitValue32(s, flags_mine_.get() + x.src * kCh + ch, ++recv_seq_[x.src][ch],
                                       hipStreamWaitValueGte, 0xffffffffu),
                  "hipStreamWaitValue32");
         } else {
           int msg = -1;
           c_->recv(&msg, sizeof msg, x.src);
           if (msg != ch * 2 + par) throw std::runtime_error("peer transport: out-of-order note");
-          hip_ok(hipStreamWaitEvent(s, peer_sent_[x.src][ch][par], 0), "hipStreamWaitEvent IPC");
+          hip_check(hipStreamWaitEvent(s, peer_sent_[x.src][ch][par], 0), "hipStreamWaitEvent IPC");
         }
       }
       if (halo) {
         const int seq = x.seq >= 0 ? x.seq : static_cast<int>(i);
-        copy2d(at(par, x.to), x.to.pitch, static_cast<char*>(slot_.at({seq, par})) + x.img0 * x.width, x.width,
+        copy2d(at(par, x.to), x.to.pitch, slot_.at({seq, par}).get() + x.img0 * x.width, x.width,
                x.width, x.height, s);
       }
     }
@@ -440,7 +439,7 @@ struct PeerTransport : DeviceBase {
     // writes, not on a stream that may itself be parked in a wait.
     if (!flags_ || !flags_mine_) return;
     const std::vector<uint32_t> top(static_cast<size_t>(np_) * kCh, 0xffffffffu);
-    (void)hipMemcpy(flags_mine_, top.data(), top.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    (void)hipMemcpy(flags_mine_.get(), top.data(), top.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
     for (int r = 0; r < np_; ++r)
       if (r != rank_ && r < static_cast<int>(flags_of_.size()) && flags_of_[r])
         (void)hipMemcpy(flags_of_[r] + rank_ * kCh, top.data(), kCh * sizeof(uint32_t), hipMemcpyHostToDevice);
@@ -448,15 +447,13 @@ struct PeerTransport : DeviceBase {
   void release() {
     for (void* p : opened_) (void)hipIpcCloseMemHandle(p);
     opened_.clear();
-    for (hipEvent_t e : opened_ev_) (void)hipEventDestroy(e);
+    for (hipEvent_t e : opened_ev_) ipc_event_close(e);
     opened_ev_.clear();
-    for (auto& kv : slot_) (void)hipFree(kv.second);
     slot_.clear();
     peer_slot_.clear();
     for (auto& ch : sent_)
-      for (auto& e : ch)
-        if (e) (void)hipEventDestroy(e), e = nullptr;
-    if (flags_mine_) (void)hipFree(flags_mine_), flags_mine_ = nullptr;
+      for (auto& e : ch) e.reset();
+    flags_mine_.reset();
     flags_of_.clear();
     connected_ = false;
   }

@@ -19,14 +19,29 @@
 namespace anx {
 
 namespace {
-void hip_ok(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("v4 ") + what + ": " + hipGetErrorString(e));
-}
+void hip_ok(hipError_t e, const char* what) { hip_check(e, (std::string("v4 ") + what).c_str()); }
 constexpr int kRing = 32;
 constexpr int kMaxChunks = 16;
+
+// The shared host segment. A base of Impl_, so it goes after every member of Impl_: the pinned registration,
+// the mapping and (rank 0, before the others opened it) the segment name outlive the engine, the device
+// buffers, the events and the streams, as far as the constructor got.
+struct Segment {
+  std::string shm_name;
+  char* seg = nullptr;
+  size_t seg_bytes = 0, in_bytes = 0, out_bytes = 0;
+  bool registered = false;
+  bool created = false;  // rank 0 created the segment name and has not unlinked it yet
+  ~Segment() {
+    if (registered) (void)hipHostUnregister(seg);
+    if (seg) munmap(seg, seg_bytes);
+    if (created) shm_unlink(shm_name.c_str());
+  }
+};
 }  // namespace
 
-struct V4Runtime::Impl_ {
+// Members are destroyed in reverse order of declaration: engine, device buffers, events, streams.
+struct V4Runtime::Impl_ : Segment {
   HostComm& c;
   RankInfo ri;
   V4Options o;
@@ -35,52 +50,23 @@ struct V4Runtime::Impl_ {
   int rank = 0, np = 1, dev = 0, C = 1, n = 0;
   TilePlan t;
   RowRange im;
-  std::unique_ptr<BlocksEngine> eng;
-  // shared segment
-  std::string shm_name;
-  char* seg = nullptr;
-  size_t seg_bytes = 0, in_bytes = 0, out_bytes = 0;
-  bool registered = false;
   size_t in_row = 0, out_row = 0;  // bytes
   size_t tin_img = 0, tout_img = 0;  // bytes of one image's tile rows (input / output)
-  float* d_in[2] = {nullptr, nullptr};
-  float* d_y[2] = {nullptr, nullptr};
   std::vector<int> lo;
-  hipStream_t sh = nullptr, st = nullptr, sd = nullptr;
-  std::vector<hipEvent_t> e_in[2], e_cmp[2], e_out[2];
   long k = 0;
-  std::vector<std::vector<hipEvent_t>> ring;
   std::vector<bool> pending;
   int ring_pos = 0;
   double sums[3] = {0, 0, 0};
   long timed = 0;
-
-  bool created = false;  // rank 0 created the segment name and has not unlinked it yet
+  HipStream sh, st, sd;
+  std::vector<std::vector<HipEvent>> ring;
+  std::vector<HipEvent> e_in[2], e_cmp[2], e_out[2];
+  DevBuf<float> d_in[2], d_y[2];
+  std::unique_ptr<BlocksEngine> eng;
 
   Impl_(HostComm& cc, const RankInfo& r, const V4Options& oo) : c(cc), ri(r), o(oo) {}
-  // Frees whatever the constructor got to (it may have thrown half way): engine, device buffers,
-  // events, streams, the pinned registration, the mapping and (rank 0, before the others opened it)
-  // the segment name.
-  ~Impl_() {
-    eng.reset();
-    for (int p = 0; p < 2; ++p) {
-      if (d_in[p]) (void)hipFree(d_in[p]);
-      if (d_y[p]) (void)hipFree(d_y[p]);
-      for (auto* v : {&e_in[p], &e_cmp[p], &e_out[p]})
-        for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-    }
-    for (auto& e : ring)
-      for (hipEvent_t v : e) (void)hipEventDestroy(v);
-    for (hipStream_t s : {sh, st, sd})
-      if (s) (void)hipStreamDestroy(s);
-    if (registered) (void)hipHostUnregister(seg);
-    if (seg) munmap(seg, seg_bytes);
-    if (created) shm_unlink(shm_name.c_str());
-  }
-  hipEvent_t event(bool timing = false) {
-    hipEvent_t e = nullptr;
-    hip_ok(hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming), "hipEventCreate");
-    return e;
+  HipEvent event(bool timing = false) {
+    return HipEvent::create(timing ? hipEventDefault : hipEventDisableTiming, "v4 hipEventCreate");
   }
   void fold(int i) {
     if (!pending[i]) return;
@@ -183,17 +169,17 @@ V4Runtime::V4Runtime(HostComm& c, const RankInfo& ri, const BlockSpec& b1, const
   I.tin_img = static_cast<size_t>(I.t.in.size()) * I.in_row;
   I.tout_img = static_cast<size_t>(I.t.out.size()) * I.out_row;
   for (int p = 0; p < 2; ++p) {
-    hip_ok(hipMalloc(&I.d_in[p], std::max<size_t>(4, I.n * I.tin_img)), "hipMalloc");
-    hip_ok(hipMalloc(&I.d_y[p], std::max<size_t>(4, I.n * I.tout_img)), "hipMalloc");
+    I.d_in[p] = DevBuf<float>(I.n * I.tin_img / 4, 4);
+    I.d_y[p] = DevBuf<float>(I.n * I.tout_img / 4, 4);
     for (int cc = 0; cc < I.C; ++cc) {
       I.e_in[p].push_back(I.event());
       I.e_cmp[p].push_back(I.event());
       I.e_out[p].push_back(I.event());
     }
   }
-  hip_ok(hipStreamCreateWithFlags(&I.sh, hipStreamNonBlocking), "hipStreamCreate");
-  hip_ok(hipStreamCreateWithFlags(&I.st, hipStreamNonBlocking), "hipStreamCreate");
-  hip_ok(hipStreamCreateWithFlags(&I.sd, hipStreamNonBlocking), "hipStreamCreate");
+  I.sh = HipStream::create();
+  I.st = HipStream::create();
+  I.sd = HipStream::create();
   I.ring.resize(kRing);
   for (auto& e : I.ring)
     for (int i = 0; i < 5; ++i) e.push_back(I.event(true));
@@ -208,7 +194,7 @@ V4Runtime::~V4Runtime() {
     p_->c.barrier();  // every rank's copies out of / into the segment are done
   } catch (...) {
   }
-  p_.reset();  // Impl_'s destructor frees everything
+  p_.reset();  // Impl_'s members, then the segment
 }
 
 float* V4Runtime::host_input() const { return reinterpret_cast<float*>(p_->seg); }
@@ -222,9 +208,9 @@ double V4Runtime::probe_h2d_gbps(int reps) {
   Impl_& I = *p_;
   sync();
   if (!I.n) return 0;
-  hipEvent_t a = I.event(true), b = I.event(true);
+  const HipEvent a = I.event(true), b = I.event(true);
   auto copy = [&] {
-    hip_ok(hipMemcpy2DAsync(I.d_in[0], I.tin_img, I.in_at(I.im.lo) + I.t.in.lo * I.in_row,
+    hip_ok(hipMemcpy2DAsync(I.d_in[0].get(), I.tin_img, I.in_at(I.im.lo) + I.t.in.lo * I.in_row,
                             static_cast<size_t>(I.d.H) * I.in_row, I.tin_img, I.n, hipMemcpyHostToDevice, I.sh),
            "H2D probe");
   };
@@ -235,8 +221,6 @@ double V4Runtime::probe_h2d_gbps(int reps) {
   hip_ok(hipEventSynchronize(b), "hipEventSynchronize");
   float ms = 0;
   hip_ok(hipEventElapsedTime(&ms, a, b), "hipEventElapsedTime");
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
   return static_cast<double>(h2d_bytes_per_step()) * reps / (ms * 1e6);
 }
 
@@ -246,7 +230,7 @@ void V4Runtime::input_ready() {
 }
 
 void V4Runtime::sync() {
-  for (hipStream_t s : {p_->sh, p_->st, p_->sd}) hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize");
+  for (hipStream_t s : {p_->sh.get(), p_->st.get(), p_->sd.get()}) hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize");
 }
 
 void V4Runtime::sync_all() {
@@ -263,8 +247,8 @@ void V4Runtime::step() {
   I.ring_pos = (I.ring_pos + 1) % kRing;
   auto wait = [](hipStream_t s, hipEvent_t ev) { hip_ok(hipStreamWaitEvent(s, ev, 0), "hipStreamWaitEvent"); };
   auto rec = [](hipEvent_t ev, hipStream_t s) { hip_ok(hipEventRecord(ev, s), "hipEventRecord"); };
-  char* din = reinterpret_cast<char*>(I.d_in[par]);
-  char* dy = reinterpret_cast<char*>(I.d_y[par]);
+  char* din = reinterpret_cast<char*>(I.d_in[par].get());
+  char* dy = reinterpret_cast<char*>(I.d_y[par].get());
   rec(e[0], I.sh);
   for (int cc = 0; cc < I.C; ++cc) {  // H2D: this rank's images x tile rows, straight from the segment
     const int a = I.lo[cc], b = I.lo[cc + 1];

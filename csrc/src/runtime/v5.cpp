@@ -15,9 +15,7 @@
 namespace anx {
 
 namespace {
-void hip_ok(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("v5 ") + what + ": " + hipGetErrorString(e));
-}
+void hip_ok(hipError_t e, const char* what) { hip_check(e, (std::string("v5 ") + what).c_str()); }
 constexpr int kB = static_cast<int>(BufId::kCount);
 constexpr int kMaxChunks = 16;  // the peer transport's halo channels
 constexpr int kRing = 32;       // per-step timing event sets kept before they are folded in
@@ -141,6 +139,10 @@ std::vector<std::string> v5_dry_schedule(int rank, int np, const BlockSpec& b1, 
 }
 
 // ------------------------------------------------------------------------------------------ runtime
+// Teardown is by member declaration order (members are destroyed in reverse): after ~Impl_'s body the
+// transport goes first, then the engines, the buffers, the events and last the streams. The owners are
+// therefore declared streams, events, buffers, engines, transport; a constructor that throws releases
+// whatever it got to in the same order.
 struct V5Runtime::Impl_ {
   HostComm& c;
   RankInfo ri;
@@ -149,8 +151,6 @@ struct V5Runtime::Impl_ {
   BlocksDims d;
   int rank = 0, np = 1, dev = 0, C = 1;
   std::string tr;
-  std::unique_ptr<Transport> x;
-  std::unique_ptr<BlocksEngine> eng;
   TilePlan t;
   int n = 0;  // images this rank computes
   // lane path: a tile that needs no halo (a row group of one rank, or overlap tiles) runs as nl
@@ -159,9 +159,6 @@ struct V5Runtime::Impl_ {
   bool lane_path = false, local = true;
   int nl = 1;  // lanes
   std::vector<int> lb;
-  std::vector<std::unique_ptr<BlocksEngine>> leng;
-  std::vector<hipStream_t> ls;
-  hipEvent_t e_lane[kMaxLanes][2] = {}, e_go[2] = {}, e_gdone[2] = {};
   std::vector<int> lo;  // this rank's chunk bounds (C + 1)
   size_t x_bytes = 0, yfull_bytes = 0, tile_bytes = 0, y_bytes = 0;
   float* d_x = nullptr;
@@ -169,33 +166,47 @@ struct V5Runtime::Impl_ {
   float* d_y[2] = {nullptr, nullptr};
   float* d_yfull[2] = {nullptr, nullptr};
   bool alias_tile = false, alias_y = false;
-  std::vector<float*> owned;  // device allocations to free
-  hipStream_t st = nullptr, io = nullptr, hs = nullptr;
+  bool built = false;  // the constructor finished: teardown takes part in the collective close
   bool aborted = false;
-  hipEvent_t e_sc[2] = {}, e_s2[2] = {}, e_hdone = nullptr;
-  std::vector<hipEvent_t> e_s1, e_h;
   long k = 0;
   bool prefetched = false;
   bool pipeline = false;
-  // timing: ring of per-step event sets (5 + 2 C events), folded into sums when reused or read
-  std::vector<std::vector<hipEvent_t>> ring;
   std::vector<bool> pending;
   int ring_pos = 0;
   double sums[5] = {0, 0, 0, 0, 0};
   long timed = 0;
+  // ---- owners, in reverse order of teardown
+  HipStream st, io, hs;
+  std::vector<HipStream> lane_s;  // streams of lanes 1..nl-1
+  std::vector<hipStream_t> ls;    // every lane's stream; ls[0] is st (not owned here)
+  HipEvent e_sc[2], e_s2[2], e_hdone;
+  std::vector<HipEvent> e_s1, e_h;
+  // timing: ring of per-step event sets (5 + 2 C events), folded into sums when reused or read
+  std::vector<std::vector<HipEvent>> ring;
+  HipEvent e_lane[kMaxLanes][2], e_go[2], e_gdone[2];
+  std::vector<DevBuf<float>> owned;  // this rank's device buffers
+  std::vector<std::unique_ptr<BlocksEngine>> leng;
+  std::unique_ptr<BlocksEngine> eng;
+  std::unique_ptr<Transport> x;
 
   Impl_(HostComm& cc, const RankInfo& r, const V5Options& oo, const V5Layout& l) : c(cc), ri(r), o(oo), L(l) {}
+  ~Impl_() {
+    (void)hipDeviceSynchronize();  // after abort() no stream waits on a peer any more
+    try {
+      if (built && !aborted) {
+        c.barrier();  // nobody pushes into a peer's buffers any more
+        x->close();   // collective: unmap, barrier, free own
+      }
+    } catch (...) {
+    }
+  }
 
   float* dalloc(size_t bytes) {
-    void* p = nullptr;
-    hip_ok(hipMalloc(&p, std::max<size_t>(bytes, 4)), "hipMalloc");
-    owned.push_back(static_cast<float*>(p));
-    return static_cast<float*>(p);
+    owned.emplace_back((bytes + 3) / 4, 4);
+    return owned.back().get();
   }
-  hipEvent_t event(bool timing = false) {
-    hipEvent_t e = nullptr;
-    hip_ok(hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming), "hipEventCreate");
-    return e;
+  HipEvent event(bool timing = false) {
+    return HipEvent::create(timing ? hipEventDefault : hipEventDisableTiming, "v5 hipEventCreate");
   }
   void rec(hipEvent_t e, hipStream_t s) { hip_ok(hipEventRecord(e, s), "hipEventRecord"); }
   void wait(hipStream_t s, hipEvent_t e) { hip_ok(hipStreamWaitEvent(s, e, 0), "hipStreamWaitEvent"); }
@@ -236,7 +247,7 @@ struct V5Runtime::Impl_ {
   // Lane path: every lane waits for its step's input (`in_ev`: the scatter / the previous gather of
   // this parity, both on io; or e_go on st when not pipelined) on its own stream and runs the fused
   // tile forward of its slice; e_lane[i][par] marks it done (the gather waits for all of them).
-  void compute_lanes(long kk, std::vector<hipEvent_t>& e, hipEvent_t in_ev) {
+  void compute_lanes(long kk, std::vector<HipEvent>& e, hipEvent_t in_ev) {
     const int par = static_cast<int>(kk & 1);
     rec(e[2], st);
     for (int cc = 0; cc < C; ++cc) rec(e[3 + 2 * cc], st), rec(e[4 + 2 * cc], st);  // no halo on this path
@@ -264,7 +275,7 @@ struct V5Runtime::Impl_ {
   }
 
   // stage1 chunks, halo chunks on hs, stage2 chunks; e: this step's timing events
-  void compute(long kk, std::vector<hipEvent_t>& e) {
+  void compute(long kk, std::vector<HipEvent>& e) {
     const int par = static_cast<int>(kk & 1);
     const bool per_layer = o.mode == Decomp::PerLayer;
     // the previous step's halo pushes read this rank's window: stage1 may rewrite it only after them
@@ -445,23 +456,22 @@ V5Runtime::V5Runtime(HostComm& c, const RankInfo& ri, const BlockSpec& b1, const
     hw = w;
   }
   if (I.np > 1) {
-    void* wd = nullptr;
-    hip_ok(hipMalloc(&wd, total * 4), "hipMalloc weights");
+    DevBuf<float> wbuf(total, 0);
+    float* const wd = wbuf.get();
     std::vector<float>* parts[4] = {&hw.w1, &hw.b1, &hw.w2, &hw.b2};
     size_t off = 0;
     if (I.rank == 0)
       for (auto* v : parts) {
-        hip_ok(hipMemcpy(static_cast<float*>(wd) + off, v->data(), v->size() * 4, hipMemcpyHostToDevice), "H2D weights");
+        hip_ok(hipMemcpy(wd + off, v->data(), v->size() * 4, hipMemcpyHostToDevice), "H2D weights");
         off += v->size();
       }
     I.x->bcast(wd, total * 4, 0);
     off = 0;
     if (I.rank != 0)
       for (auto* v : parts) {
-        hip_ok(hipMemcpy(v->data(), static_cast<float*>(wd) + off, v->size() * 4, hipMemcpyDeviceToHost), "D2H weights");
+        hip_ok(hipMemcpy(v->data(), wd + off, v->size() * 4, hipMemcpyDeviceToHost), "D2H weights");
         off += v->size();
       }
-    hip_ok(hipFree(wd), "hipFree");
   }
 
   const HybridPlan& hp = lay_.plan;
@@ -476,14 +486,13 @@ V5Runtime::V5Runtime(HostComm& c, const RankInfo& ri, const BlockSpec& b1, const
   I.eng = std::make_unique<BlocksEngine>(b1, b2, H, W, hw, std::max(1, I.lb[1] - I.lb[0]), o.impl, o.knobs);
   for (int i = 1; i < I.nl; ++i)
     I.leng.push_back(std::make_unique<BlocksEngine>(b1, b2, H, W, hw, std::max(1, I.lb[i + 1] - I.lb[i]), o.impl, o.knobs));
-  hip_ok(hipStreamCreateWithFlags(&I.st, hipStreamNonBlocking), "hipStreamCreate");
-  hip_ok(hipStreamCreateWithFlags(&I.io, hipStreamNonBlocking), "hipStreamCreate");
-  hip_ok(hipStreamCreateWithFlags(&I.hs, hipStreamNonBlocking), "hipStreamCreate");
+  I.st = HipStream::create();
+  I.io = HipStream::create();
+  I.hs = HipStream::create();
   I.ls.push_back(I.st);
   for (int i = 1; i < I.nl; ++i) {
-    hipStream_t s = nullptr;
-    hip_ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
-    I.ls.push_back(s);
+    I.lane_s.push_back(HipStream::create());
+    I.ls.push_back(I.lane_s.back());
   }
 
   const BlocksDims& d = I.d;
@@ -534,39 +543,10 @@ V5Runtime::V5Runtime(HostComm& c, const RankInfo& ri, const BlockSpec& b1, const
     for (int i = 0; i < 5 + 2 * I.C; ++i) e.push_back(I.event(true));
   I.pending.assign(kRing, false);
   c.barrier();
+  I.built = true;
 }
 
-V5Runtime::~V5Runtime() {
-  if (!p_) return;
-  Impl_& I = *p_;
-  (void)hipDeviceSynchronize();  // after abort() no stream waits on a peer any more
-  try {
-    if (!I.aborted) {
-      I.c.barrier();  // nobody pushes into a peer's buffers any more
-      I.x->close();   // collective: unmap, barrier, free own
-    }
-  } catch (...) {
-  }
-  I.x.reset();
-  I.eng.reset();
-  I.leng.clear();
-  for (float* p : I.owned) (void)hipFree(p);
-  for (int p = 0; p < 2; ++p) {
-    for (hipEvent_t v : {I.e_go[p], I.e_gdone[p]})
-      if (v) (void)hipEventDestroy(v);
-    for (int i = 0; i < kMaxLanes; ++i)
-      if (I.e_lane[i][p]) (void)hipEventDestroy(I.e_lane[i][p]);
-  }
-  for (size_t i = 1; i < I.ls.size(); ++i) (void)hipStreamDestroy(I.ls[i]);
-  for (auto& e : I.ring)
-    for (hipEvent_t v : e) (void)hipEventDestroy(v);
-  for (hipEvent_t v : I.e_s1) (void)hipEventDestroy(v);
-  for (hipEvent_t v : I.e_h) (void)hipEventDestroy(v);
-  for (hipEvent_t v : {I.e_sc[0], I.e_sc[1], I.e_s2[0], I.e_s2[1], I.e_hdone})
-    if (v) (void)hipEventDestroy(v);
-  for (hipStream_t s : {I.st, I.io, I.hs})
-    if (s) (void)hipStreamDestroy(s);
-}
+V5Runtime::~V5Runtime() = default;  // ~Impl_, then its members in their order
 
 const char* V5Runtime::transport() const { return h_ ? h_->x->name() : p_->x->name(); }
 long V5Runtime::steps() const { return h_ ? h_->k : p_->k; }
@@ -612,7 +592,7 @@ void V5Runtime::step() {
   const int par = static_cast<int>(k & 1);
   const int slot = I.ring_pos;
   I.fold(slot);
-  std::vector<hipEvent_t>& e = I.ring[slot];
+  std::vector<HipEvent>& e = I.ring[slot];
   I.ring_pos = (I.ring_pos + 1) % kRing;
   if (!I.pipeline) {  // every phase in step order on the compute stream (side lanes fork from it)
     I.rec(e[0], I.st);
@@ -676,7 +656,7 @@ void V5Runtime::abort() {
 void V5Runtime::sync() {
   if (h_) return;  // host mode: blocking phases
   Impl_& I = *p_;
-  for (hipStream_t s : {I.st, I.io, I.hs}) hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize");
+  for (hipStream_t s : {I.st.get(), I.io.get(), I.hs.get()}) hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize");
   for (size_t i = 1; i < I.ls.size(); ++i) hip_ok(hipStreamSynchronize(I.ls[i]), "hipStreamSynchronize");
 }
 

@@ -134,8 +134,16 @@ Options parse(int argc, char** argv) {
   return o;
 }
 
-void hip_check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+// Pinned host memory (hipHostMalloc) for the I/O buffers of the V3 / V4 programs
+struct PinnedFree {
+  static void* null() noexcept { return nullptr; }
+  static void free(void* p) noexcept { (void)hipHostFree(p); }
+};
+using PinnedBuf = Owned<void*, PinnedFree>;
+PinnedBuf pinned(size_t bytes, const char* what) {
+  void* p = nullptr;
+  hip_check(hipHostMalloc(&p, bytes, hipHostMallocDefault), what);
+  return PinnedBuf(p);
 }
 
 uint32_t crc32(const void* data, size_t n) {
@@ -367,22 +375,20 @@ int run_single(Setup& s) {
     hip_check(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
     if (ndev < 1) throw std::runtime_error("v3 needs a GPU");
     hip_check(hipSetDevice(s.ri.local_rank % ndev), "hipSetDevice");
-    hipStream_t st;
-    hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "stream");
+    const HipStream st = HipStream::create();
     cold.add("init", now_ms() - a0);
     a0 = now_ms();
     set_upload_stream(st);  // the engine's weight uploads on this stream (the null stream's first use costs a queue)
     BlocksEngine eng(s.b1, s.b2, s.d.H, s.d.W, s.w, N, s.o.impl == "direct" ? Impl::Direct : Impl::Mfma, s.k);
     cold.add("engine", now_ms() - a0);
     a0 = now_ms();
-    float *dx, *dy, *hx, *hy;
-    hip_check(hipMalloc(&dx, s.x.size() * 4), "hipMalloc");
-    hip_check(hipMalloc(&dy, y.size() * 4), "hipMalloc");
+    const DevBuf<float> dxb(s.x.size(), 0), dyb(y.size(), 0);
+    float *const dx = dxb.get(), *const dy = dyb.get();
     // pinned I/O buffers: a copy from pageable memory would initialise the runtime's staged-copy path
     // inside the timed region (9-10 ms on its first use, anx/upload.hpp); the image is written into the
     // pinned buffer on the host, as a serving process receives it
-    hip_check(hipHostMalloc(reinterpret_cast<void**>(&hx), s.x.size() * 4, hipHostMallocDefault), "hipHostMalloc");
-    hip_check(hipHostMalloc(reinterpret_cast<void**>(&hy), y.size() * 4, hipHostMallocDefault), "hipHostMalloc");
+    const PinnedBuf hxb = pinned(s.x.size() * 4, "hipHostMalloc"), hyb = pinned(y.size() * 4, "hipHostMalloc");
+    float *const hx = static_cast<float*>(hxb.get()), *const hy = static_cast<float*>(hyb.get());
     std::memcpy(hx, s.x.data(), s.x.size() * 4);
     cold.add("alloc", now_ms() - a0);
     auto step = [&](Phases& ph) {
@@ -403,13 +409,8 @@ int run_single(Setup& s) {
     cold_ms = now_ms() - t0;
     for (int i = 0; i < s.o.iters; ++i) step(warm);
     std::memcpy(y.data(), hy, y.size() * 4);
-    hip_check(hipFree(dx), "free");
-    hip_check(hipFree(dy), "free");
-    hip_check(hipHostFree(hx), "free");
-    hip_check(hipHostFree(hy), "free");
     set_upload_stream(nullptr);
-    hip_check(hipStreamDestroy(st), "free");
-  }
+  }  // the I/O buffers, the engine, then the stream
   warm_ms = s.o.iters ? warm.total() / s.o.iters : 0;
   report(s, 1, y, cold_ms, warm_ms, cold, warm, s.o.iters, s.o.check ? check_err(s, y) : -1);
   return 0;
@@ -463,8 +464,10 @@ int run_rows_host(Setup& s, HostComm& c, bool gpu) {
   cold.add("bcast", now_ms() - a);
   a = now_ms();
   std::unique_ptr<CpuBlocks> ceng;
+  HipStream st;
   std::unique_ptr<BlocksEngine> geng;
-  hipStream_t st = nullptr;
+  DevBuf<float> d_in_buf, d_y_buf;
+  PinnedBuf h_in_buf, h_y_buf;
   float *d_in = nullptr, *d_y = nullptr, *h_in = nullptr, *h_y = nullptr;
   std::vector<float> tile_in(static_cast<size_t>(N) * t.in.size() * s.in_row);
   std::vector<float> y_loc(static_cast<size_t>(N) * t.out.size() * s.out_row);
@@ -474,13 +477,15 @@ int run_rows_host(Setup& s, HostComm& c, bool gpu) {
     hip_check(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
     if (ndev < 1) throw std::runtime_error("v4 needs a GPU");
     hip_check(hipSetDevice(s.ri.local_rank % ndev), "hipSetDevice");  // fixes reference D4
-    hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "stream");
+    st = HipStream::create();
     geng = std::make_unique<BlocksEngine>(s.b1, s.b2, s.d.H, s.d.W, s.w, N,
                                           s.o.impl == "direct" ? Impl::Direct : Impl::Mfma, s.k);
-    hip_check(hipMalloc(&d_in, std::max<size_t>(1, tile_in.size()) * 4), "hipMalloc");
-    hip_check(hipMalloc(&d_y, std::max<size_t>(1, y_loc.size()) * 4), "hipMalloc");
-    hip_check(hipHostMalloc(&h_in, std::max<size_t>(1, tile_in.size()) * 4, hipHostMallocDefault), "pinned");
-    hip_check(hipHostMalloc(&h_y, std::max<size_t>(1, y_loc.size()) * 4, hipHostMallocDefault), "pinned");
+    d_in_buf = DevBuf<float>(tile_in.size());
+    d_y_buf = DevBuf<float>(y_loc.size());
+    h_in_buf = pinned(std::max<size_t>(1, tile_in.size()) * 4, "pinned");
+    h_y_buf = pinned(std::max<size_t>(1, y_loc.size()) * 4, "pinned");
+    d_in = d_in_buf.get(), d_y = d_y_buf.get();
+    h_in = static_cast<float*>(h_in_buf.get()), h_y = static_cast<float*>(h_y_buf.get());
   } else {
     ceng = std::make_unique<CpuBlocks>(s.b1, s.b2, s.d.H, s.d.W, s.w);
   }
@@ -671,15 +676,8 @@ int run_rows_host(Setup& s, HostComm& c, bool gpu) {
   double tm[2] = {cold_ms, s.o.iters ? warm.total() / s.o.iters : 0};
   c.allreduce_max(tm, 2);
   if (rank == 0) report(s, np, y_full, tm[0], tm[1], cold, warm, s.o.iters, s.o.check ? check_err(s, y_full) : -1);
-  if (gpu) {
-    (void)hipFree(d_in);
-    (void)hipFree(d_y);
-    (void)hipHostFree(h_in);
-    (void)hipHostFree(h_y);
-    (void)hipStreamDestroy(st);
-  }
   c.barrier();
-  return 0;
+  return 0;  // the I/O buffers, the engine, then the stream
 }
 
 // ------------------------------------------------------------------------------ V5 (device-resident)

@@ -56,6 +56,8 @@ _SIGS = {
     "anx_last_error": (C.c_char_p, []),
     "anx_abi_version": (_I, []),
     "anx_device_count": (_I, []),
+    "anx_device_live": (_I, [C.POINTER(_SZ)]),
+    "anx_device_fail_alloc": (_I, [_I]),
     "anx_default_blocks": (None, [C.POINTER(BlockC), C.POINTER(BlockC)]),
     "anx_make_plan": (_I, [_I, _I, _I, _I, C.POINTER(BlockC), C.POINTER(BlockC), C.POINTER(TileC), C.POINTER(_I),
                            C.POINTER(_I), C.POINTER(XferC), C.POINTER(_I), C.POINTER(XferC), C.POINTER(_I), _I]),
