@@ -158,6 +158,21 @@ class FullEngine {
   // freed with the engine), never inside a stream capture: warm up once before capturing a graph.
   hipError_t forward_u8(const uint8_t* x, int N, float* logits, hipStream_t s, bool mark = false);
   void set_input_norm(const float* scale, const float* offset);  // three values each
+  // The classifier head on top of forward / forward_u8: idx int32 [N][k] and prob fp32 [N][k] device, the k most
+  // likely classes of each image and their softmax probabilities (cpu::softmax_topk is the definition; 1 <= k <=
+  // min(classes, kMaxTopK), else hipErrorInvalidValue). logits (nullable): [N,classes] fp32 device, the bits
+  // forward() writes. The same layer chain as forward: chunking (outputs advance by n * k per chunk), mark,
+  // last_input() and last_path() are forward's. Where FC8 went through split-K slabs, the head kernel reduces them
+  // itself with FC8's bias in place of splitk_reduce_bf16 (Knobs::bf16_head; 0: the reduce writes the logits and
+  // the head runs on those); where FC8 writes fp32 directly the head runs on the logits. Logits nobody asked for
+  // go to a workspace the constructor allocated: no call allocates, so a call can be captured into a graph.
+  hipError_t classify(const float* x, int N, int k, int* idx, float* prob, float* logits, hipStream_t s,
+                      bool mark = false);
+  hipError_t classify_u8(const uint8_t* x, int N, int k, int* idx, float* prob, float* logits, hipStream_t s,
+                         bool mark = false);
+  // What the head of the last call read: "slabs" (it reduced FC8's split-K slabs), "logits" (written logits), null
+  // when the last call was forward / forward_u8. Recorded at the launch from host state.
+  const char* last_head() const { return head_; }
   // How the last forward's input reached Conv1: "f32", "u8_ring", "u8_decode"; null before the first. Recorded at
   // the launch site from host state.
   const char* last_input() const { return input_; }
@@ -188,13 +203,24 @@ class FullEngine {
     int key = -1;
     std::vector<float> host;  // KCFF fp32 (re-pack when the tile variant changes)
   };
+  // classify's outputs for the launch chunk at hand; slabs: set by conv() when the head kernel took FC8's slabs
+  struct Head {
+    int k;
+    int* idx;
+    float* prob;
+    float* logits;  // nullable
+    bool slabs;
+  };
   hipError_t conv(Layer& L, int N, int Hp, int Wp, const void* x, hip::OutViewB out, float* out_f32, bool relu,
-                  hipStream_t s);
-  // the one layer chain: exactly one of xf (floats) / xu (bytes) is set
-  hipError_t run(const float* xf, const uint8_t* xu, int N, float* logits, hipStream_t s, bool mark);
+                  hipStream_t s, Head* head = nullptr);
+  // the one layer chain: exactly one of xf (floats) / xu (bytes) is set; head: classify's outputs (whole call)
+  hipError_t run(const float* xf, const uint8_t* xu, int N, float* logits, hipStream_t s, bool mark,
+                 const Head* head = nullptr);
   hip::U8Norm norm_{3, {1.f / 255.f, 1.f / 255.f, 1.f / 255.f}, {0.f, 0.f, 0.f}};  // byte input: scale / offset
   DevBuf<float> xdec_;             // byte input decoded to fp32 (u8_decode), chunk_ images, allocated on first need
   const char* input_ = nullptr;    // last_input()
+  const char* head_ = nullptr;     // last_head()
+  DevBuf<float> hlog_;             // classify: a launch chunk's logits [chunk_][classes] when the caller takes none
   Layer L_[8];
   FullPathRecord path_;
   Knobs k_;

@@ -91,6 +91,15 @@ int anx_engine_last_input(void* e, char* buf, size_t cap);
    (device, 1 <= C <= 16; host, any C) */
 int anx_decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, const float* offset, void* stream);
 int anx_cpu_decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, const float* offset);
+/* the classifier head: for each of M rows, z[c] = bias[c] + src[0][m][c] + ... + src[ksplit-1][m][c] (slab s at
+   src + s * slab_stride floats; fp32 adds in that order; bias may be null: the sum then starts from slab 0, so
+   ksplit = 1 without a bias passes logits through), idx [M][k] int32 = the k best classes by value descending then
+   index ascending (-0.0 and +0.0 tie), prob [M][k] = their softmax probabilities, logits_out (nullable) [M][K] = z.
+   1 <= k <= min(K, 16). On the device a row of more than 15360 floats needs logits_out (it is staged there). */
+int anx_softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k,
+                     int* idx, float* prob, float* logits_out, void* stream);
+int anx_cpu_softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k,
+                         int* idx, float* prob, float* logits_out);
 /* conv2 input window geometry: pointer of (image n, pool1 row r), row stride and image stride (floats). */
 int anx_engine_window(void* e, const anx_tile_c* t, int n, int r, float** ptr, size_t* row_floats,
                       size_t* image_floats);
@@ -117,6 +126,17 @@ int anx_full_forward_u8(void* e, const uint8_t* x, int N, float* logits, void* s
 int anx_full_forward_mark_u8(void* e, const uint8_t* x, int N, float* logits, void* stream);
 int anx_full_set_input_norm(void* e, const float* scale, const float* offset);
 int anx_full_last_input(void* e, char* buf, size_t cap);
+/* The classifier head on top of forward / forward_u8 (same chunking, mark, last_input and last_path): idx [N][k]
+   int32 and prob [N][k] fp32 on the device, the k most likely classes per image (value descending, then index
+   ascending) and their softmax probabilities, 1 <= k <= min(classes, 16); logits (nullable) [N][classes] = the
+   bits anx_full_forward writes. Knob bf16_head = 1: where FC8 went through split-K slabs the head kernel reduces
+   them itself; 0: the reduce writes the logits first; same bits. No call allocates. anx_full_last_head writes
+   "slabs" or "logits" (what the last call's head read; "" after a plain forward) into buf; no device call. */
+int anx_full_classify(void* e, const float* x, int N, int k, int* idx, float* prob, float* logits, void* stream,
+                      int mark);
+int anx_full_classify_u8(void* e, const uint8_t* x, int N, int k, int* idx, float* prob, float* logits, void* stream,
+                         int mark);
+int anx_full_last_head(void* e, char* buf, size_t cap);
 
 /* ---- host engine (same contract as the device engine; V1 / V2 CPU ranks) ---- */
 int anx_cpu_engine_create(void** out, const anx_block_c* b1, const anx_block_c* b2, int H, int W, const float* w1,

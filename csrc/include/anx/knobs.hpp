@@ -52,6 +52,9 @@ struct Knobs {
                            // byte kernel alone 89.6 us against 59.3 us of decode + 88.2 us of the float kernel behind
                            // it (100.7 us on floats that no decode just wrote); host-fed 1.35 ms as bytes vs 3.48 ms
                            // as floats (profiles/bf16_u8_input/)
+  int bf16_head = 1;       // bf16 classifier head (FullEngine::classify) where FC8 went through split-K slabs: 1 = the
+                           // head kernel reduces the slabs itself (the logits never reach HBM unless asked for),
+                           // 0 = the split-K reduce writes the logits and the head runs on them. Same bits either way
   int conv1_occ = 0;       // cap on the Conv1 Winograd GEMM's workgroups per CU (LDS padding; 0 = none: 4)
   int conv2_occ = -1;      // ... and Conv2's (0 = none: 2; -1 = auto: 1 when the launch has <= one workgroup per
                            // CU); a cap leaves room for a concurrent lane's kernels

@@ -33,6 +33,20 @@ void lrn(const float* x, float* y, int N, int H, int W, int C, int size, float a
 // THE definition of the byte input's meaning: hip::decode_u8 and the byte loader of the one-kernel Conv1
 // evaluate the same expression, so every path is comparable bit for bit. The reference has no byte input.
 void decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, const float* offset);
+// Top-k class probabilities of M rows of K logits. THE definition of the classifier head: hip::softmax_topk
+// computes the same logits bits and the same indices. Per row m:
+//   z[c]   = bias[c] + src[0][m][c] + ... + src[ksplit-1][m][c] over the split-K slabs src[s] = src + s *
+//            slab_stride (floats), fp32 adds in exactly that order (splitk_reduce_bf16's); without a bias the sum
+//            starts from slab 0, so logits pass through with their bits (ksplit 1, bias null);
+//   idx[j] = the k best classes by value descending, then index ascending; float comparison, so -0.0 and +0.0 tie
+//            (a NaN ranks below everything, as -inf does, so a row of any values yields k distinct indices);
+//   prob[j] = exp(z[idx[j]] - max) / sum_c exp(z[c] - max) in fp32 (unspecified for a row holding a NaN or
+//            whose maximum is infinite).
+// 1 <= k <= min(K, kMaxTopK). idx int32 [M][k], prob [M][k], logits_out (nullable) [M][K] = the bits of z.
+// The reference ends at Block 2's LRN and has no classifier head.
+constexpr int kMaxTopK = 16;
+void softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k, int* idx,
+                  float* prob, float* logits_out);
 }  // namespace cpu
 
 // ----------------------------------------------------------------------------------------
@@ -184,6 +198,16 @@ hipError_t conv1_fused_u8(const Conv1WinoPlan& w, const uint8_t* x, const U8Norm
 hipError_t conv1_fused_pool_u8(const Conv1WinoPlan& w, const uint8_t* x, const U8Norm& nm, const float* U,
                                const float* bias, OutView window, float* p1, int Hp, int Wp, bool relu, hipStream_t s,
                                int um = 0);
+
+// The classifier head (softmax_topk.hip; cpu::softmax_topk is the definition): one workgroup per row reduces the
+// split-K slabs (+ bias) once, keeps the row in LDS, and writes the k best classes and their softmax probabilities;
+// logits_out (nullable) receives the reduced row. A row's result depends only on the bits of its logits, not on
+// M, the row's position, or whether it came from slabs or a logits array. Rows of more than kSoftmaxTopkLdsRow
+// floats are staged in logits_out instead of LDS: without one the call returns hipErrorInvalidValue, as it does
+// for k or K out of range and null idx / prob / src. M == 0 launches nothing.
+constexpr int kSoftmaxTopkLdsRow = 15 * 1024;
+hipError_t softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k,
+                        int* idx, float* prob, float* logits_out, hipStream_t s);
 
 // The fused Winograd GEMM + output transform (wino_gemm.hip). V [P][points][C], U [points][K][C/groups]
 // (row = filter), bias + optional ReLU, NHWC store through `out` (Cb, c_off multiples of 4). P tiles of

@@ -122,7 +122,9 @@ const char* anx_last_error(void) { return g_err.c_str(); }
 // 3: byte input of the bf16 full model (anx_full_forward_u8, anx_full_forward_mark_u8, anx_full_set_input_norm,
 //    anx_full_last_input; knob bf16_u8)
 // 4: device-owner diagnostics (anx_device_live, anx_device_fail_alloc)
-int anx_abi_version(void) { return 4; }
+// 5: the classifier head (anx_softmax_topk, anx_cpu_softmax_topk, anx_full_classify, anx_full_classify_u8,
+//    anx_full_last_head; knob bf16_head)
+int anx_abi_version(void) { return 5; }
 
 int anx_device_live(size_t out[4]) {
   if (!out) return fail("anx_device_live: no buffer");
@@ -298,6 +300,41 @@ int anx_cpu_decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* 
   return guarded("anx_cpu_decode_u8", [&] {
     if (C < 1 || !scale || !offset) return fail("anx_cpu_decode_u8: C >= 1 scale / offset values");
     anx::cpu::decode_u8(x, y, n, C, scale, offset);
+    return 0;
+  });
+}
+
+namespace {
+// the argument checks both softmax_topk entries share; 0 = fine
+int softmax_topk_args(const std::string& fn, const float* src, int ksplit, int M, int K, int k, const int* idx,
+                      const float* prob) {
+  if (K < 1) return fail(fn + ": K >= 1 classes");
+  if (k < 1 || k > anx::cpu::kMaxTopK || k > K) return fail(fn + ": 1 <= k <= min(K, 16)");
+  if (ksplit < 1) return fail(fn + ": ksplit >= 1 slabs");
+  if (M < 0) return fail(fn + ": M >= 0 rows");
+  if (M > 0 && !src) return fail(fn + ": no source");
+  if (M > 0 && (!idx || !prob)) return fail(fn + ": no output buffer (idx, prob)");
+  return 0;
+}
+}  // namespace
+
+int anx_softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k,
+                     int* idx, float* prob, float* logits_out, void* stream) {
+  return guarded("anx_softmax_topk", [&] {
+    if (softmax_topk_args("anx_softmax_topk", src, ksplit, M, K, k, idx, prob)) return 1;
+    if (K > anx::hip::kSoftmaxTopkLdsRow && !logits_out)
+      return fail("anx_softmax_topk: a row of more than " + std::to_string(anx::hip::kSoftmaxTopkLdsRow) +
+                  " floats is staged in logits_out, which is null");
+    return hip_status(anx::hip::softmax_topk(src, ksplit, slab_stride, bias, M, K, k, idx, prob, logits_out, S(stream)),
+                      "anx_softmax_topk");
+  });
+}
+
+int anx_cpu_softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k,
+                         int* idx, float* prob, float* logits_out) {
+  return guarded("anx_cpu_softmax_topk", [&] {
+    if (softmax_topk_args("anx_cpu_softmax_topk", src, ksplit, M, K, k, idx, prob)) return 1;
+    anx::cpu::softmax_topk(src, ksplit, slab_stride, bias, M, K, k, idx, prob, logits_out);
     return 0;
   });
 }

@@ -110,6 +110,51 @@ int anx_full_last_input(void* e, char* buf, size_t cap) {
   });
 }
 
+namespace {
+// the argument checks of the two classify entries; 0 = fine
+int classify_args(const std::string& fn, void* e, const void* x, int N, int k, const int* idx, const float* prob) {
+  if (!e) return fail(fn + ": no engine");
+  const int classes = static_cast<anx::FullEngine*>(e)->classes();
+  if (k < 1 || k > anx::cpu::kMaxTopK || k > classes)
+    return fail(fn + ": 1 <= k <= min(classes, 16), got k = " + std::to_string(k) + " for " + std::to_string(classes) +
+                " classes");
+  if (N > 0 && (!x || !idx || !prob)) return fail(fn + ": no buffer (x, idx, prob)");
+  return 0;
+}
+}  // namespace
+
+int anx_full_classify(void* e, const float* x, int N, int k, int* idx, float* prob, float* logits, void* stream,
+                      int mark) {
+  return guarded("anx_full_classify", [&] {
+    if (classify_args("anx_full_classify", e, x, N, k, idx, prob)) return 1;
+    return hip_status(static_cast<anx::FullEngine*>(e)->classify(x, N, k, idx, prob, logits, S(stream), mark != 0),
+                      "anx_full_classify");
+  });
+}
+
+int anx_full_classify_u8(void* e, const uint8_t* x, int N, int k, int* idx, float* prob, float* logits, void* stream,
+                         int mark) {
+  return guarded("anx_full_classify_u8", [&] {
+    if (classify_args("anx_full_classify_u8", e, x, N, k, idx, prob)) return 1;
+    return hip_status(static_cast<anx::FullEngine*>(e)->classify_u8(x, N, k, idx, prob, logits, S(stream), mark != 0),
+                      "anx_full_classify_u8");
+  });
+}
+
+// What the head of the last call read ("" after a plain forward and before the first call). Host state only.
+int anx_full_last_head(void* e, char* buf, size_t cap) {
+  return guarded("anx_full_last_head", [&] {
+    if (!e) return fail("anx_full_last_head: no engine");
+    if (!buf || cap == 0) return fail("anx_full_last_head: no buffer");
+    const char* v = static_cast<anx::FullEngine*>(e)->last_head();
+    const std::string j = v ? v : "";
+    if (j.size() + 1 > cap) return fail("anx_full_last_head: buffer too small");
+    j.copy(buf, j.size());
+    buf[j.size()] = 0;
+    return 0;
+  });
+}
+
 int anx_full_wait_mark(void* e, void* stream) {
   return guarded("anx_full_wait_mark", [&] {
     return hip_status(static_cast<anx::FullEngine*>(e)->wait_mark(S(stream)), "full wait mark");

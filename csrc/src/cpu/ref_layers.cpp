@@ -23,6 +23,62 @@ void decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, 
   }
 }
 
+namespace {
+// fp32 pairwise sum: the error grows with log2(n) roundings, not n
+float pairwise_sum(const float* v, size_t n) {
+  if (n <= 8) {
+    float s = 0.f;
+    for (size_t i = 0; i < n; ++i) s += v[i];
+    return s;
+  }
+  const size_t h = n / 2;
+  return pairwise_sum(v, h) + pairwise_sum(v + h, n - h);
+}
+}  // namespace
+
+void softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k, int* idx,
+                  float* prob, float* logits_out) {
+  const float inf = std::numeric_limits<float>::infinity();
+  std::vector<float> z(static_cast<size_t>(K)), e(static_cast<size_t>(K));
+  for (int m = 0; m < M; ++m) {
+    const float* x = src + static_cast<size_t>(m) * K;
+    for (int c = 0; c < K; ++c) {
+      float v;
+      int s = 0;
+      if (bias) {
+        v = bias[c];
+      } else {
+        v = x[c];
+        s = 1;
+      }
+      for (; s < ksplit; ++s) v = v + x[s * slab_stride + c];
+      z[c] = v;
+    }
+    if (logits_out) std::copy(z.begin(), z.end(), logits_out + static_cast<size_t>(m) * K);
+    float mx = -inf;
+    for (int c = 0; c < K; ++c)
+      if (z[c] > mx) mx = z[c];
+    for (int c = 0; c < K; ++c) e[c] = std::exp(z[c] - mx);
+    const float sum = pairwise_sum(e.data(), e.size());
+    // round j: the best element ranking strictly after round j-1's winner (value descending, index ascending;
+    // a NaN ranks with -inf, so the order is total)
+    float pv = inf;
+    int pi = -1;
+    for (int j = 0; j < k; ++j) {
+      float bv = -inf;
+      int bi = K;
+      for (int c = 0; c < K; ++c) {
+        const float v = z[c] != z[c] ? -inf : z[c];
+        if ((v < pv || (v == pv && c > pi)) && (bi == K || v > bv)) bv = v, bi = c;
+      }
+      pv = bv;
+      pi = bi;
+      idx[static_cast<size_t>(m) * k + j] = bi;
+      prob[static_cast<size_t>(m) * k + j] = std::exp(z[bi] - mx) / sum;
+    }
+  }
+}
+
 void conv2d(const float* x, const float* w, const float* b, float* y, int N, int H, int W, int C, int K, int F,
             int S, int P, int groups, bool relu, int pad_top, int pad_bottom) {
   const int pt = pad_top < 0 ? P : pad_top;

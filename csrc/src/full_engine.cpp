@@ -101,10 +101,11 @@ FullEngine::FullEngine(const FullWeights& w, int classes, int max_batch, int gro
       }
     }
   if (ws) ws_ = DevBuf<float>(ws, 16);
+  hlog_ = DevBuf<float>(n * static_cast<size_t>(classes), 16);  // classify without a caller's logits buffer
 }
 
 hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip::OutViewB out, float* out_f32,
-                            bool relu, hipStream_t s) {
+                            bool relu, hipStream_t s, Head* head) {
   auto B = [](void* q) { return static_cast<__bf16*>(q); };
   const hip::ConvPlanB p = hip::make_conv_plan_bf16(N, Hp, Wp, L.C, L.K, L.F, L.S, L.groups);
   if (p.variant != L.key) {  // pack for this tile variant (first use / batch-size class change)
@@ -136,6 +137,17 @@ hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip:
     rec.splitk = ksplit;
     return e;
   };
+  // classify with bf16_head: the head kernel reduces the slabs [ksplit][N][K] (+ bias) in place of the reduce. A row
+  // too long for its LDS is staged in the logits buffer, which out_f32 always is under classify.
+  auto reduce = [&](int ksplit) {
+    if (head && k_.bf16_head) {
+      head->slabs = true;
+      float* lo = head->logits ? head->logits : L.K > hip::kSoftmaxTopkLdsRow ? out_f32 : nullptr;
+      return hip::softmax_topk(ws_.get(), ksplit, static_cast<size_t>(N) * L.K, L.bias.get(), N, L.K, head->k, head->idx,
+                               head->prob, lo, s);
+    }
+    return hip::splitk_reduce_bf16(ws_.get(), ksplit, N, L.K, L.bias.get(), relu, out, out_f32, s);
+  };
   if (fc && k_.bf16_big != -2) {  // wide-tile FC: one 256-row tile of the batch, K split over the CUs
     hip::BigFc f = hip::pick_bf16_big_fc(p, cus_, k_.bf16_fc_cfg, k_.bf16_fc_minkt);
     if (f.cfg >= 0 && k_.bf16_big >= 0 && hip::conv_bf16_big_ok(p, k_.bf16_big, hip::OutViewB{B(ws_.get()), 1, 1, p.Kg, 0, 0, 0}))
@@ -143,7 +155,7 @@ hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip:
     if (f.cfg >= 0 && (f.ksplit > 1 || out_f32)) {
       ANX_TRY(hip::conv2d_bf16_big(p, f.cfg, x, L.wp.get(), L.koff.get(), L.bias.get(), hip::OutViewB{B(ws_.get()), 1, 1, p.Kg, 0, 0, 0}, relu,
                                    s, hip::SplitK{f.ksplit, ws_.get()}, big(f.ksplit)));
-      return hip::splitk_reduce_bf16(ws_.get(), f.ksplit, N, L.K, L.bias.get(), relu, out, out_f32, s);
+      return reduce(f.ksplit);
     }
     if (f.cfg >= 0) return hip::conv2d_bf16_big(p, f.cfg, x, L.wp.get(), L.koff.get(), L.bias.get(), out, relu, s, {}, big(1));
   }
@@ -151,7 +163,7 @@ hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip:
   if (ks > 1) {  // FC layer at a small batch: K split over ~one workgroup per CU, then a reduce
     ANX_TRY(tile(ks, hip::conv2d_bf16(p, x, L.wp.get(), L.koff.get(), L.bias.get(), out, out_f32, relu, s, hip::SplitK{ks, ws_.get()},
                                       k_.bf16_glds, &rec.id)));
-    return hip::splitk_reduce_bf16(ws_.get(), ks, N, L.K, L.bias.get(), relu, out, out_f32, s);
+    return reduce(ks);
   }
   if (!fc && !out_f32 && k_.bf16_big != -2) {  // wide-tile kernel: forced config if it applies, else the cost model
     const int cfg = k_.bf16_big >= 0 && hip::conv_bf16_big_ok(p, k_.bf16_big, out) ? k_.bf16_big
@@ -169,11 +181,27 @@ hipError_t FullEngine::forward_u8(const uint8_t* x, int N, float* logits, hipStr
   return run(nullptr, x, N, logits, s, mark);
 }
 
+hipError_t FullEngine::classify(const float* x, int N, int k, int* idx, float* prob, float* logits, hipStream_t s,
+                                bool mark) {
+  const Head h{k, idx, prob, logits, false};
+  return run(x, nullptr, N, logits, s, mark, &h);
+}
+
+hipError_t FullEngine::classify_u8(const uint8_t* x, int N, int k, int* idx, float* prob, float* logits, hipStream_t s,
+                                   bool mark) {
+  const Head h{k, idx, prob, logits, false};
+  return run(nullptr, x, N, logits, s, mark, &h);
+}
+
 void FullEngine::set_input_norm(const float* scale, const float* offset) {
   for (int c = 0; c < 3; ++c) norm_.sc[c] = scale[c], norm_.of[c] = offset[c];
 }
 
-hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* logits, hipStream_t s, bool mark) {
+hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* logits, hipStream_t s, bool mark,
+                           const Head* head) {
+  if (head && (head->k < 1 || head->k > cpu::kMaxTopK || head->k > classes_ || (N > 0 && (!head->idx || !head->prob))))
+    return hipErrorInvalidValue;
+  head_ = nullptr;
   if (mark && !mark_) ANX_TRY(mark_.try_create(hipEventDisableTiming));
   using hip::OutViewB;
   auto B = [](void* p) { return static_cast<__bf16*>(p); };
@@ -241,8 +269,20 @@ hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* log
     ANX_TRY(hip::maxpool_bf16(c5_, n, 13, 13, 256, 3, 2, OutViewB{B(f6_), 6, 6, 256, 0, 0, 0}, s));
     ANX_TRY(conv(L_[5], n, 1, 1, f6_, OutViewB{B(f7_), 1, 1, 4096, 0, 0, 0}, nullptr, true, s));
     ANX_TRY(conv(L_[6], n, 1, 1, f7_, OutViewB{B(f8_), 1, 1, 4096, 0, 0, 0}, nullptr, true, s));
-    ANX_TRY(conv(L_[7], n, 1, 1, f8_, OutViewB{nullptr, 1, 1, classes_, 0, 0, 0},
-                 logits + static_cast<size_t>(n0) * classes_, false, s));
+    if (!head) {
+      ANX_TRY(conv(L_[7], n, 1, 1, f8_, OutViewB{nullptr, 1, 1, classes_, 0, 0, 0},
+                   logits + static_cast<size_t>(n0) * classes_, false, s));
+      continue;
+    }
+    // classify: this chunk's outputs; logits the caller does not take go to the workspace
+    Head h{head->k, head->idx + static_cast<size_t>(n0) * head->k, head->prob + static_cast<size_t>(n0) * head->k,
+           logits ? logits + static_cast<size_t>(n0) * classes_ : nullptr, false};
+    float* const z = h.logits ? h.logits : hlog_.get();
+    ANX_TRY(conv(L_[7], n, 1, 1, f8_, OutViewB{nullptr, 1, 1, classes_, 0, 0, 0}, z, false, s, &h));
+    if (!h.slabs)  // on the written logits (a row too long for the head's LDS is read back from them)
+      ANX_TRY(hip::softmax_topk(z, 1, 0, nullptr, n, classes_, h.k, h.idx, h.prob,
+                                classes_ > hip::kSoftmaxTopkLdsRow ? z : nullptr, s));
+    head_ = h.slabs ? "slabs" : "logits";
   }
   return hipSuccess;
 }

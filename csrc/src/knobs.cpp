@@ -34,6 +34,7 @@ const Field kFields[] = {
     {"bf16_conv1", &Knobs::bf16_conv1, nullptr, 0, 2, "ANX_BF16_CONV1"},
     {"bf16_pool1", &Knobs::bf16_pool1, nullptr, 0, 1, "ANX_BF16_POOL1"},
     {"bf16_u8", &Knobs::bf16_u8, nullptr, 0, 1, "ANX_BF16_U8"},
+    {"bf16_head", &Knobs::bf16_head, nullptr, 0, 1, "ANX_BF16_HEAD"},
     {"conv1_occ", &Knobs::conv1_occ, nullptr, 0, 8, "ANX_CONV1_OCC"},
     {"conv2_occ", &Knobs::conv2_occ, nullptr, -1, 8, "ANX_CONV2_OCC"},
     {"conv1_band", &Knobs::conv1_band, nullptr, 0, 2, "ANX_CONV1_BAND"},

@@ -83,6 +83,8 @@ _SIGS = {
     "anx_engine_last_input": (_I, [_P, C.c_char_p, _SZ]),
     "anx_decode_u8": (_I, [_P, _P, _SZ, _I, _P, _P, _P]),
     "anx_cpu_decode_u8": (_I, [_P, _P, _SZ, _I, _P, _P]),
+    "anx_softmax_topk": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "anx_cpu_softmax_topk": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _P, _P, _P]),
     "anx_cpu_engine_set_input_norm": (_I, [_P, _P, _P]),
     "anx_cpu_engine_forward_u8": (_I, [_P, _P, _I, _P]),
     "anx_cpu_engine_tile_forward_u8": (_I, [_P, _P, _I, C.POINTER(TileC), _P]),
@@ -174,6 +176,9 @@ _BF16_SIGS = {
     "anx_full_forward_mark_u8": (_I, [_P, _P, _I, _P, _P]),
     "anx_full_set_input_norm": (_I, [_P, _P, _P]),
     "anx_full_last_input": (_I, [_P, C.c_char_p, _SZ]),
+    "anx_full_classify": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I]),
+    "anx_full_classify_u8": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I]),
+    "anx_full_last_head": (_I, [_P, C.c_char_p, _SZ]),
 }
 _bf16 = None
 

@@ -158,13 +158,16 @@ class AlexNetFull:
         except Exception:
             pass
 
-    def _check(self, x: torch.Tensor, out: torch.Tensor | None) -> torch.Tensor:
-        """The engine reads x and writes out through raw pointers: both must be exactly what the
-        kernels assume (shape, dtype, contiguity, device)."""
+    def _check_x(self, x: torch.Tensor) -> None:
         if (x.dim() != 4 or tuple(x.shape[1:]) != (227, 227, 3) or x.dtype not in (torch.float32, torch.uint8)
                 or not x.is_contiguous() or x.device != self.device):
             raise ValueError(f"expected contiguous fp32 (or uint8: byte images) NHWC [N,227,227,3] on {self.device}, got "
                              f"{tuple(x.shape)} {x.dtype} on {x.device}")
+
+    def _check(self, x: torch.Tensor, out: torch.Tensor | None) -> torch.Tensor:
+        """The engine reads x and writes out through raw pointers: both must be exactly what the
+        kernels assume (shape, dtype, contiguity, device)."""
+        self._check_x(x)
         shape = (x.shape[0], self.classes)
         if out is None:
             return torch.empty(shape, device=self.device)
@@ -237,6 +240,111 @@ class AlexNetFull:
                 if on_lane is not None:
                     on_lane(i, lo, hi)
         return out
+
+    def _check_head(self, x, k, idx, prob):
+        """classify's outputs: validated like ``out`` in :meth:`_check`, allocated when not given."""
+        if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= min(self.classes, 16):
+            raise ValueError(f"k must be an integer with 1 <= k <= min(classes, 16) = {min(self.classes, 16)}, got {k!r}")
+        shape = (x.shape[0], k)
+        outs = []
+        for t, dt, name in ((idx, torch.int32, "indices"), (prob, torch.float32, "probabilities")):
+            if t is None:
+                t = torch.empty(shape, device=self.device, dtype=dt)
+            elif tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"{name} must be a contiguous {dt} {shape} tensor on {self.device}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            outs.append(t)
+        return outs
+
+    def classify(self, x: torch.Tensor, k: int = 5, *, return_logits: bool = False, out=None):
+        """x as in :meth:`forward` -> ``(indices [N,k] int32, probs [N,k] fp32)``: the ``k`` most likely classes of
+        each image (logit descending, then class index ascending) and their softmax probabilities, equal bit for bit
+        to ``anx.ops.softmax_topk(forward(x), k)``. ``return_logits`` appends the ``[N, classes]`` logits, the bits
+        :meth:`forward` gives. ``out``: ``(indices, probs)`` or ``(indices, probs, logits)`` tensors to write into.
+        Where FC8 ran split-K, the head kernel reduces the slabs itself (knob ``bf16_head``), so without
+        ``return_logits`` the logits never reach device memory; :meth:`last_head` tells. Lanes as :meth:`forward`."""
+        out = tuple(out) if out is not None else ()
+        if len(out) not in (0, 2, 3):
+            raise ValueError("out must be (indices, probs) or (indices, probs, logits)")
+        want_logits = return_logits or len(out) == 3
+        self._check_x(x)
+        z = self._check(x, out[2] if len(out) == 3 else None) if want_logits else None
+        idx, prob = self._check_head(x, k, *(out[:2] if out else (None, None)))
+        self._classify(x, k, idx, prob, z)
+        return (idx, prob, z) if want_logits else (idx, prob)
+
+    def _classify(self, x, k, idx, prob, z):
+        N = x.shape[0]
+        fn = "anx_full_classify_u8" if x.dtype == torch.uint8 else "anx_full_classify"
+        zp = z.data_ptr() if z is not None else None
+        L = 1 + len(self._lanes)
+        if L == 1 or N < L:
+            self._ensure(N)
+            nat.call(fn, self._h, x.data_ptr(), N, k, idx.data_ptr(), prob.data_ptr(), zp,
+                     nat.stream_ptr(self.device), 0)
+            return
+        bounds = [N * i // L for i in range(L + 1)]
+        cur = torch.cuda.current_stream(self.device)
+        for i, st in enumerate(self._lane_streams, start=1):
+            st.wait_stream(cur)  # fork: inputs produced / outputs free on the current stream
+            lo, hi = bounds[i], bounds[i + 1]
+            with torch.cuda.stream(st):
+                self._lanes[i - 1]._classify(x[lo:hi], k, idx[lo:hi], prob[lo:hi], z[lo:hi] if z is not None else None)
+        self._ensure(bounds[1])
+        nat.call(fn, self._h, x.data_ptr(), bounds[1], k, idx.data_ptr(), prob.data_ptr(), zp,
+                 nat.stream_ptr(self.device), 0)
+        for st in self._lane_streams:
+            cur.wait_stream(st)  # join
+
+    def classify_async(self, x: torch.Tensor, idx_out: torch.Tensor, prob_out: torch.Tensor, k: int = 5, on_lane=None,
+                       pre_lane=None):
+        """:meth:`classify` in the throughput form of :meth:`forward_async` (same contract: free-running lanes on
+        their own streams, lane i starting at lane i-1's mid-forward mark when all are idle, never joined per call):
+        writes ``idx_out`` ``[N,k]`` int32 and ``prob_out`` ``[N,k]`` fp32. :meth:`join` before reading them."""
+        self._check_x(x)
+        idx_out, prob_out = self._check_head(x, k, idx_out, prob_out)
+        N = x.shape[0]
+        L = 1 + len(self._lanes)
+        if L == 1 or N < L or self.device.type != "cuda":
+            if pre_lane is not None:
+                pre_lane(0, 0, N)
+            self._classify(x, k, idx_out, prob_out, None)
+            if on_lane is not None:
+                on_lane(0, 0, N)
+            return idx_out, prob_out
+        if getattr(self, "_own_stream", None) is None:
+            self._own_stream = torch.cuda.Stream(self.device)
+        streams = [self._own_stream, *self._lane_streams]
+        engines = [self, *self._lanes]
+        bounds = self.lane_bounds(N)
+        fresh = all(st.query() for st in streams)
+        cur = torch.cuda.current_stream(self.device)
+        fn = "anx_full_classify_u8" if x.dtype == torch.uint8 else "anx_full_classify"
+        for i, (eng, st) in enumerate(zip(engines, streams)):
+            lo, hi = bounds[i], bounds[i + 1]
+            eng._ensure(hi - lo)
+            if fresh:
+                st.wait_stream(cur)
+                if i > 0:
+                    nat.call("anx_full_wait_mark", engines[i - 1]._h, st.cuda_stream)
+            with torch.cuda.stream(st):
+                if pre_lane is not None:
+                    pre_lane(i, lo, hi)
+                nat.call(fn, eng._h, x[lo:hi].data_ptr(), hi - lo, k, idx_out[lo:hi].data_ptr(),
+                         prob_out[lo:hi].data_ptr(), None, st.cuda_stream, int(fresh and i + 1 < L))
+                if on_lane is not None:
+                    on_lane(i, lo, hi)
+        return idx_out, prob_out
+
+    def last_head(self, lane: int = 0) -> str | None:
+        """What the head of the last call of this model's engine (``lane`` > 0: that side lane's) read: ``"slabs"``
+        (it reduced FC8's split-K slabs itself), ``"logits"`` (logits FC8 or the split-K reduce wrote), ``None`` when
+        that call was a plain forward. Recorded at the launch; reading it makes no device call."""
+        if lane:
+            return self._lanes[lane - 1].last_head()
+        buf = C.create_string_buffer(32)
+        nat.call("anx_full_last_head", self._h, buf, len(buf))
+        return buf.value.decode() or None
 
     def lane_bounds(self, n: int) -> list[int]:
         """Image boundaries [0, ..., n] of the lanes :meth:`forward_async` runs ``n`` images on (the

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from .. import _native as nat
 from ..config import conv_out_dim, pool_out_dim
 
-__all__ = ["conv2d", "relu", "maxpool", "lrn", "maxpool_lrn", "decode_u8", "clear_cache"]
+__all__ = ["conv2d", "relu", "maxpool", "lrn", "maxpool_lrn", "decode_u8", "softmax_topk", "clear_cache"]
 
 _LRN_MODES = {"div_n": 0, "raw": 1}
 _pack_cache: dict = {}
@@ -134,6 +134,57 @@ def decode_u8(x: torch.Tensor, scale=None, offset=None) -> torch.Tensor:
     else:
         nat.call("anx_cpu_decode_u8", x.data_ptr(), y.data_ptr(), x.numel(), sc.numel(), sc.data_ptr(), of.data_ptr())
     return y
+
+
+MAX_TOPK = 16          # kMaxTopK (anx/ops.hpp)
+_HEAD_LDS_ROW = 15 * 1024  # kSoftmaxTopkLdsRow: a longer row is staged in the logits output on the GPU
+
+
+def softmax_topk(logits: torch.Tensor | None = None, k: int = 5, *, slabs: torch.Tensor | None = None,
+                 bias: torch.Tensor | None = None, return_logits: bool = False):
+    """The classifier head: the ``k`` most likely classes of each row and their softmax probabilities, one native
+    kernel. Returns ``(indices int32 [M,k], probs float32 [M,k])``, plus the ``[M,K]`` logits with ``return_logits``.
+
+    The rows are ``logits`` ``[M,K]``, or the sum ``bias + slabs[0] + slabs[1] + ...`` of split-K partial sums
+    ``slabs`` ``[ksplit,M,K]`` (fp32 adds in that order, the order of the bf16 engine's split-K reduce; ``bias``
+    ``[K]`` is optional). Classes are ordered by value descending, then index ascending; values compare as floats, so
+    ``-0.0`` and ``+0.0`` tie. ``p = exp(z - max) / sum(exp(z - max))`` in fp32. ``1 <= k <= min(K, 16)``. A row that
+    holds a NaN or whose maximum is infinite still gets ``k`` distinct indices; its probabilities are unspecified.
+    The host function ``cpu::softmax_topk`` (CPU tensors) is the definition the GPU kernel is tested against."""
+    if (logits is None) == (slabs is None):
+        raise ValueError("softmax_topk: give logits [M,K] or slabs [ksplit,M,K], not both")
+    src = logits if slabs is None else slabs
+    _check(src, "softmax_topk")
+    if slabs is None:
+        if src.dim() != 2:
+            raise ValueError("softmax_topk: logits must be [M,K]")
+        if bias is not None:
+            raise ValueError("softmax_topk: a bias goes with slabs")
+        ksplit, (M, K) = 1, src.shape
+    else:
+        if src.dim() != 3 or src.shape[0] < 1:
+            raise ValueError("softmax_topk: slabs must be [ksplit,M,K] with ksplit >= 1")
+        ksplit, M, K = src.shape
+    if K < 1 or not 1 <= int(k) <= min(K, MAX_TOPK):
+        raise ValueError(f"softmax_topk: need 1 <= k <= min(K, {MAX_TOPK}), got k = {k} for K = {K}")
+    if bias is not None:
+        _check(bias, "softmax_topk bias")
+        if tuple(bias.shape) != (K,) or bias.device != src.device:
+            raise ValueError("softmax_topk: bias must be [K] on the source's device")
+    k = int(k)
+    idx = torch.empty((M, k), device=src.device, dtype=torch.int32)
+    prob = torch.empty((M, k), device=src.device, dtype=torch.float32)
+    z = None
+    if return_logits or (src.is_cuda and K > _HEAD_LDS_ROW):
+        z = torch.empty((M, K), device=src.device, dtype=torch.float32)
+    if M:
+        args = (src.data_ptr(), ksplit, M * K, bias.data_ptr() if bias is not None else None, M, K, k, idx.data_ptr(),
+                prob.data_ptr(), z.data_ptr() if z is not None else None)
+        if src.is_cuda:
+            nat.call("anx_softmax_topk", *args, nat.stream_ptr(src.device))
+        else:
+            nat.call("anx_cpu_softmax_topk", *args)
+    return (idx, prob, z) if return_logits else (idx, prob)
 
 
 def relu(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:

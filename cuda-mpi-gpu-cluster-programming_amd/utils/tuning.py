@@ -37,7 +37,10 @@ Names and values:
   kernel, 1 = the kernel loads and decodes the bytes itself; same bits); ``bf16_u8`` (0 / 1: byte input of the bf16
   full model where Conv1 is the row-band kernel on the image, ``bf16_conv1`` 2: 1 = that kernel loads and decodes
   the bytes itself, 0 = the decode kernel into a workspace and then the float kernel; same bits; the default is
-  set by measurement, ``profiles/bf16_u8_input/``).
+  set by measurement, ``profiles/bf16_u8_input/``); ``bf16_head`` (0 / 1: the classifier head of the bf16 full
+  model, ``AlexNetFull.classify``, where FC8 went through split-K slabs: 1 = the head kernel reduces the slabs
+  itself and the logits reach memory only when asked for, 0 = the split-K reduce writes the logits and the head
+  runs on them; same bits; ``profiles/classify_head/``).
 """
 from __future__ import annotations
 
@@ -49,7 +52,7 @@ ALGOS = {"auto": 0, "direct": 1, "winograd": 2}
 KNOBS = ("conv1_algo", "conv2_algo", "chunk1", "chunk2", "force_vec4", "force_scalar", "bf16_glds", "bf16_big",
          "bf16_lrn_tile", "bf16_conv1", "bf16_pool1", "bf16_fc_cfg", "bf16_fc_minkt", "conv1_occ", "conv2_occ", "conv1_band", "fuse_pool1", "conv1_sub", "conv2_sub",
          "conv1_fused", "conv1_pool", "conv1_u8", "conv2_pool", "conv2_tile", "conv2_sched", "conv2_in_pg", "lrn_wgs",
-         "bf16_u8")
+         "bf16_u8", "bf16_head")
 
 
 def knob_value(name: str, value) -> int:
@@ -60,7 +63,7 @@ def knob_value(name: str, value) -> int:
         if value not in ALGOS:
             raise ValueError(f"{name} must be one of {sorted(ALGOS)}")
         return ALGOS[value]
-    if name == "bf16_u8" and int(value) not in (0, 1):
+    if name in ("bf16_u8", "bf16_head") and int(value) not in (0, 1):
         raise ValueError(f"{name} must be 0 or 1")
     return int(value)
 
