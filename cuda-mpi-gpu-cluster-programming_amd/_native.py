@@ -265,6 +265,13 @@ def call(name: str, *args) -> None:
     check(getattr(bf16() if name in _BF16_SIGS else lib(), name)(*args), name)
 
 
+def read_str(name: str, handle, cap: int) -> str | None:
+    """What the native ``name(handle, buffer, cap)`` writes into its buffer, decoded; ``None`` if nothing."""
+    buf = C.create_string_buffer(cap)
+    call(name, handle, buf, cap)
+    return buf.value.decode() or None
+
+
 def ptr(t) -> int:
     """Raw data pointer of a torch tensor (must be contiguous)."""
     if not t.is_contiguous():

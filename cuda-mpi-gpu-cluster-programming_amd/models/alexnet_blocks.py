@@ -19,7 +19,9 @@ lane fill the CUs the MFMA GEMMs of the other leave idle in their tail waves
 results are bit-identical to one lane. :meth:`forward_async` is the throughput form for repeated
 forwards: the lanes are not joined per call but run free on their own streams, started half a
 forward apart, so one lane's HBM-bound kernels overlap the other's GEMMs in steady state
-(``profiles/r02_lanes_async.txt``: 128 images 0.629 -> 0.561 ms per forward). On the CPU it runs libanx's C++ host engine (CpuBlocks). There is no eager-PyTorch
+(``profiles/r02_lanes_async.txt``: 128 images 0.629 -> 0.561 ms per forward). Which stream waits for what
+in either form is defined in :mod:`anx.models.lanes`; this model supplies the per-lane engine calls. On the
+CPU it runs libanx's C++ host engine (CpuBlocks). There is no eager-PyTorch
 fallback: the PyTorch oracle lives in :mod:`anx.models.reference` and is only used by tests.
 
 Byte images: every entry point that takes the image (``forward``, ``forward_async``, ``tile_forward``,
@@ -44,6 +46,7 @@ from ..config import IN_H, IN_W, BlockSpec, blocks, blocks_dims
 from ..parallel.plan import TilePlan, full_plan
 from ..utils.init import init_weights
 from ..utils.tuning import apply_knobs, knob_value, read_knob
+from .lanes import Lanes, handover, split
 
 IMPLS = {"mfma": 0, "direct": 1}
 LANE_MIN = 16  # images per lane below which a forward stays on one stream (Winograd needs > 8)
@@ -53,9 +56,7 @@ def split_lanes(n: int, lanes: int) -> list[int]:
     """Image boundaries [0, ..., n] of ``n`` images over ``lanes`` stream lanes: one lane below
     ``lanes * LANE_MIN`` images, else contiguous near-equal slices (pure arithmetic: the CPU tests check
     the multi-GPU root share against it without a GPU)."""
-    if lanes <= 1 or n < lanes * LANE_MIN:
-        return [0, n]
-    return [n * i // lanes for i in range(lanes + 1)]
+    return split(n, lanes, LANE_MIN)
 
 
 def norm_scale_offset(input_norm, channels: int) -> tuple[torch.Tensor, torch.Tensor]:
@@ -137,16 +138,13 @@ class AlexNetBlocks:
         self._ensure(max(per_lane, min(max_batch, lanes * LANE_MIN - 1)) if multi else max_batch)
         # side lanes (GPU only): engines for slices 1..L-1, each on its own stream; slice 0 runs here
         self._lanes: list[AlexNetBlocks] = []
-        self._lane_streams: list[torch.cuda.Stream] = []
         if multi:
             _check_hw_queues(lanes)
             for _ in range(lanes - 1):
                 self._lanes.append(AlexNetBlocks(self.weights, specs=(self.b1, self.b2), H=H, W=W, device=self.device,
                                                  impl=impl, max_batch=per_lane, knobs=self.knobs,
                                                  input_norm=input_norm))
-                # lane_priority < 0: side lanes on high-priority streams (their waves dispatch first)
-                self._lane_streams.append(torch.cuda.Stream(self.device, priority=lane_priority))
-        self._own_stream = None  # lane 0's stream in forward_async (the joined forward uses the current one)
+        self._streams = Lanes(self.device, 1 + len(self._lanes), LANE_MIN, lane_priority)
         # forward_async from idle lanes: all lanes start together (False, default) or lane i after lane
         # i-1's stage 1, half a forward apart (True). With the fused transforms the staggered start no
         # longer pays in steady state (257.2 / 256.0 k vs 258.3 / 257.5 k images/s over 200 steps) and
@@ -196,11 +194,7 @@ class AlexNetBlocks:
         reading it makes no device call."""
         if not self.is_cuda:
             raise ValueError("last_input belongs to the GPU engine")
-        if lane:
-            return self._lanes[lane - 1].last_input()
-        buf = C.create_string_buffer(32)
-        nat.call("anx_engine_last_input", self._engine, buf, len(buf))
-        return buf.value.decode() or None
+        return nat.read_str("anx_engine_last_input", self._lane(lane)._engine, 32)
 
     def get_knob(self, name: str) -> int:
         """The value the GPU engine launches with."""
@@ -216,12 +210,8 @@ class AlexNetBlocks:
         it launches (not from the eligibility rules), and reading it makes no device call."""
         if not self.is_cuda:
             raise ValueError("last_path belongs to the GPU engine")
-        if lane:
-            return self._lanes[lane - 1].last_path()
         import json
-        buf = C.create_string_buffer(256)
-        nat.call("anx_engine_last_path", self._engine, buf, len(buf))
-        return json.loads(buf.value.decode())
+        return json.loads(nat.read_str("anx_engine_last_path", self._lane(lane)._engine, 256))
 
     # ------------------------------------------------------------------ engine lifetime
     def _ensure(self, n: int) -> None:
@@ -295,99 +285,58 @@ class AlexNetBlocks:
 
     # ------------------------------------------------------------------ forward paths
     def forward(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        """Full images: [N,H,W,3] -> [N,Hp2,Wp2,K2]."""
+        """Full images: [N,H,W,3] -> [N,Hp2,Wp2,K2]. With lanes, forked from and joined back to the current
+        stream (:meth:`anx.models.lanes.Lanes.run_joined`)."""
         plan = full_plan(self.H, self.W, self.b1, self.b2)
         if plan.inp.size != self.H and x.dim() == 4 and x.shape[1] == self.H:
             # a spec whose receptive field skips the last input rows (e.g. a 2x2 pool1): the tile reads
             # exactly the rows it needs
             x = x[:, plan.inp.lo:plan.inp.hi].contiguous()
-        L = 1 + len(self._lanes)
-        N = x.shape[0] if x.dim() == 4 else 0
-        if L == 1 or N < L * LANE_MIN:
-            return self.tile_forward(x, plan, out)
-        self._check_in(x, plan.inp.size)
+        N = self._check_in(x, plan.inp.size)
         y = self._out(out, N)
-        bounds = [N * i // L for i in range(L + 1)]
-        cur = torch.cuda.current_stream(self.device)
-        for i, st in enumerate(self._lane_streams, start=1):
-            st.wait_stream(cur)  # fork: inputs produced / outputs free on the current stream
-            lo, hi = bounds[i], bounds[i + 1]
-            with torch.cuda.stream(st):
-                self._lanes[i - 1].tile_forward(x[lo:hi], plan, y[lo:hi])
-        self.tile_forward(x[:bounds[1]], plan, y[:bounds[1]])
-        for st in self._lane_streams:
-            cur.wait_stream(st)  # join: later work on the current stream (incl. reuse of x / y) follows
+        self._streams.run_joined(N, lambda i, lo, hi: self._lane(i).tile_forward(x[lo:hi], plan, y[lo:hi]))
         return y
 
     __call__ = forward
 
     def forward_async(self, x: torch.Tensor, out: torch.Tensor, on_lane=None, pre_lane=None) -> torch.Tensor:
-        """Throughput form of :meth:`forward` for a loop of forwards on the same buffers.
-
-        Each lane enqueues its slice on its own stream and is NOT joined back: consecutive calls
-        pipeline instead of being realigned by a join every call. When every lane is idle (the first
-        call, or after any device synchronisation) the lanes fork from the current stream; with
-        ``stagger`` set, lane i >= 1 then starts when lane i-1's stage 1 (Conv1 + Pool1) is done, half
-        a forward apart (one lane's transforms and pools under the other's GEMMs), else together.
-
-        Contract: ``out`` holds a call's results once :meth:`join` has made the current stream wait
-        for the lanes (or after a device synchronisation); ``x`` and ``out`` must not be written by
-        other work until then. ``pre_lane(i, lo, hi)`` / ``on_lane(i, lo, hi)``, if given, run with
-        lane i's stream current right before / after it enqueues images [lo, hi) (e.g. waiting for a
-        collective still reading that output slice / a per-lane collective on it)."""
-        L = 1 + len(self._lanes)
+        """Throughput form of :meth:`forward` for a loop of forwards on the same buffers: free-running lanes,
+        never joined per call (contract and hooks: :meth:`anx.models.lanes.Lanes.run_free`). With ``stagger``
+        set, lane i >= 1 of idle lanes starts when lane i-1's stage 1 (Conv1 + Pool1) is done, else together.
+        :meth:`join` before reading ``out``."""
         N = self._check_in(x, self.H)
         out = self._out(out, N)
-        if L == 1 or N < L * LANE_MIN or not self.is_cuda:
-            if pre_lane is not None:
-                pre_lane(0, 0, N)
-            y = self.forward(x, out)
-            if on_lane is not None:
-                on_lane(0, 0, N)
-            return y
-        if self._own_stream is None:
-            self._own_stream = torch.cuda.Stream(self.device)
-        streams = [self._own_stream, *self._lane_streams]
-        engines = [self, *self._lanes]
         plan = full_plan(self.H, self.W, self.b1, self.b2)
-        bounds = self.lane_bounds(N)
-        fresh = all(st.query() for st in streams)
-        cur = torch.cuda.current_stream(self.device)
-        ev = None
-        for i, (eng, st) in enumerate(zip(engines, streams)):
-            lo, hi = bounds[i], bounds[i + 1]
-            with torch.cuda.stream(st):
-                if fresh:
-                    st.wait_stream(cur)  # inputs produced / outputs free on the current stream
-                    if ev is not None:
-                        st.wait_event(ev)
-                if pre_lane is not None:
-                    pre_lane(i, lo, hi)
-                if fresh and i + 1 < L and self.stagger:
-                    eng.stage1(x[lo:hi], plan)  # = tile_forward as stage1 + stage2, with the phase event between
-                    ev = torch.cuda.Event()
-                    ev.record(st)
-                    eng.stage2(hi - lo, plan, out[lo:hi])
-                else:
-                    eng.tile_forward(x[lo:hi], plan, out[lo:hi])
-                if on_lane is not None:
-                    on_lane(i, lo, hi)
+
+        def run(i, lo, hi, st, lead):
+            if st is None:  # too few images to split (or the CPU engine): the joined forward
+                self.forward(x, out)
+            elif lead and self.stagger:
+                # = tile_forward as stage1 + stage2, with the phase event between
+                self._lane(i).stage1(x[lo:hi], plan)
+                wait = handover(st)
+                self._lane(i).stage2(hi - lo, plan, out[lo:hi])
+                return wait
+            else:
+                self._lane(i).tile_forward(x[lo:hi], plan, out[lo:hi])
+
+        self._streams.run_free(N, run, pre_lane, on_lane)
         return out
 
     def lane_bounds(self, n: int) -> list[int]:
         """Image boundaries [0, ..., n] of the lanes :meth:`forward_async` runs ``n`` images on."""
-        return split_lanes(n, 1 + len(self._lanes) if self.is_cuda else 1)
+        return self._streams.bounds(n)
 
     def join(self) -> None:
         """Make the current stream wait for every lane of :meth:`forward_async`."""
-        if not self.is_cuda:
-            return
-        cur = torch.cuda.current_stream(self.device)
-        for st in ([self._own_stream] if self._own_stream is not None else []) + self._lane_streams:
-            cur.wait_stream(st)
+        self._streams.join()
 
     def lane_count(self) -> int:
         return 1 + len(self._lanes)
+
+    def _lane(self, i: int) -> "AlexNetBlocks":
+        """The model whose engine runs lane ``i``: this one for lane 0, else a side lane's."""
+        return self._lanes[i - 1] if i else self
 
     def tile_forward(self, x: torch.Tensor, tile: TilePlan, out: torch.Tensor | None = None) -> torch.Tensor:
         """Row tile: ``x`` holds input rows ``tile.inp`` of N images; returns output rows ``tile.out``."""

@@ -27,6 +27,7 @@ from .. import _native as nat
 from ..utils.init import STREAM_EXTRA, uniform
 from ..utils.tuning import apply_knobs, knob_value
 from .alexnet_blocks import norm_scale_offset
+from .lanes import Lanes
 
 LAYERS = ("conv1", "conv2", "conv3", "conv4", "conv5", "fc6", "fc7", "fc8")
 FLOPS_PER_IMAGE = 2.0 * (55 * 55 * 96 * 363 + 27 * 27 * 256 * 2400 + 13 * 13 * 384 * 2304 + 13 * 13 * 384 * 3456 +
@@ -76,17 +77,20 @@ class AlexNetFull:
         per_lane = -(-max(1, max_batch) // lanes)
         self._ensure(per_lane)  # lane 0's share; a forward of more images on lane 0 alone grows it
         # lanes > 1: the batch is split over engines on concurrent HIP streams (forked from / joined to
-        # the caller's stream, as AlexNetBlocks does), so one lane's partial last rounds overlap the
+        # the caller's stream; anx.models.lanes defines the order), so one lane's partial last rounds overlap the
         # other's kernels. Measured slower at 256 images (281k vs 305k img/s: half-size launches of
         # the 1-workgroup-per-CU kernels quantize worse), 334k at 512 as 2 x 256
         # (profiles/r02_ab_full_lanes.txt)
         self._lanes: list[AlexNetFull] = []
-        self._lane_streams: list[torch.cuda.Stream] = []
         for _ in range(lanes - 1):
             self._lanes.append(AlexNetFull(self.weights, classes=classes, device=self.device, max_batch=per_lane,
                                            groups2=groups2, lrn_mode=lrn_mode, knobs=self.knobs,
                                            input_norm=input_norm))
-            self._lane_streams.append(torch.cuda.Stream(self.device))
+        self._streams = Lanes(self.device, lanes, 1)  # any batch of at least one image per lane is split
+
+    def _lane(self, i: int) -> "AlexNetFull":
+        """The model whose engine runs lane ``i``: this one for lane 0, else a side lane's."""
+        return self._lanes[i - 1] if i else self
 
     def _ensure(self, n):
         """Grow THIS engine to n images (the other lanes' engines are untouched)."""
@@ -138,11 +142,7 @@ class AlexNetFull:
         """How the last forward of this model's engine (``lane`` > 0: that side lane's) fed Conv1: ``"f32"`` (float
         input), ``"u8_ring"`` (the row-band Conv1 loaded the bytes), ``"u8_decode"`` (decode kernel, then the float
         path); ``None`` before the first. Recorded at the launch; reading it makes no device call."""
-        if lane:
-            return self._lanes[lane - 1].last_input()
-        buf = C.create_string_buffer(32)
-        nat.call("anx_full_last_input", self._h, buf, len(buf))
-        return buf.value.decode() or None
+        return nat.read_str("anx_full_last_input", self._lane(lane)._h, 32)
 
     def close(self):
         for m in getattr(self, "_lanes", ()):
@@ -180,66 +180,56 @@ class AlexNetFull:
     def forward(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """x: [N,227,227,3] fp32 (or uint8: byte images) NHWC on the device -> logits [N, classes] fp32."""
         y = self._check(x, out)
-        N = x.shape[0]
-        fwd = "anx_full_forward_u8" if x.dtype == torch.uint8 else "anx_full_forward"
-        L = 1 + len(self._lanes)
-        if L == 1 or N < L:
-            self._ensure(N)
-            nat.call(fwd, self._h, x.data_ptr(), N, y.data_ptr(), nat.stream_ptr(self.device))
-            return y
-        bounds = [N * i // L for i in range(L + 1)]
-        cur = torch.cuda.current_stream(self.device)
-        for i, st in enumerate(self._lane_streams, start=1):
-            st.wait_stream(cur)  # fork: inputs produced / outputs free on the current stream
-            with torch.cuda.stream(st):
-                self._lanes[i - 1].forward(x[bounds[i]:bounds[i + 1]], y[bounds[i]:bounds[i + 1]])
-        self._ensure(bounds[1])
-        nat.call(fwd, self._h, x.data_ptr(), bounds[1], y.data_ptr(), nat.stream_ptr(self.device))
-        for st in self._lane_streams:
-            cur.wait_stream(st)  # join
+        self._run(x, y, None)
         return y
 
     __call__ = forward
 
     def forward_async(self, x: torch.Tensor, out: torch.Tensor, on_lane=None, pre_lane=None) -> torch.Tensor:
-        """Throughput form for repeated forwards on the same buffers (contract of
-        AlexNetBlocks.forward_async): lanes on their own streams, never joined per call; when all are
-        idle they fork from the current stream and lane i starts at lane i-1's mid-forward mark
+        """Throughput form for repeated forwards on the same buffers (contract and hooks:
+        :meth:`anx.models.lanes.Lanes.run_free`): lanes on their own streams, never joined per call; when all
+        are idle they fork from the current stream and lane i starts at lane i-1's mid-forward mark
         (after Conv2 + Pool2/LRN), so they run half a forward apart. :meth:`join` before reading out."""
         out = self._check(x, out)
-        N = x.shape[0]
-        L = 1 + len(self._lanes)
-        if L == 1 or N < L or self.device.type != "cuda":
-            if pre_lane is not None:
-                pre_lane(0, 0, N)
-            self.forward(x, out)
-            if on_lane is not None:
-                on_lane(0, 0, N)
-            return out
-        if getattr(self, "_own_stream", None) is None:
-            self._own_stream = torch.cuda.Stream(self.device)
-        streams = [self._own_stream, *self._lane_streams]
-        engines = [self, *self._lanes]
-        bounds = self.lane_bounds(N)
-        fresh = all(st.query() for st in streams)
-        cur = torch.cuda.current_stream(self.device)
-        for i, (eng, st) in enumerate(zip(engines, streams)):
-            lo, hi = bounds[i], bounds[i + 1]
-            eng._ensure(hi - lo)
-            if fresh:
-                st.wait_stream(cur)
-                if i > 0:
-                    nat.call("anx_full_wait_mark", engines[i - 1]._h, st.cuda_stream)
-            fn = "anx_full_forward_mark" if fresh and i + 1 < L else "anx_full_forward"
-            if x.dtype == torch.uint8:
-                fn += "_u8"
-            with torch.cuda.stream(st):
-                if pre_lane is not None:
-                    pre_lane(i, lo, hi)
-                nat.call(fn, eng._h, x[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr(), st.cuda_stream)
-                if on_lane is not None:
-                    on_lane(i, lo, hi)
+        self._run(x, out, None, True, pre_lane, on_lane)
         return out
+
+    def _launch(self, x, z, head, stream, mark: bool) -> None:
+        """This engine's one native call on images ``x`` (the only place that names the entry points): the forward
+        into logits ``z``, or with ``head = (k, indices, probs)`` the classify call (``z`` may be None). ``stream``
+        None: the current stream. ``mark``: record the mid-forward mark that ``anx_full_wait_mark`` waits for."""
+        u8 = x.dtype == torch.uint8
+        if stream is None:
+            stream = nat.stream_ptr(self.device)
+        if head is None:
+            if mark:
+                fn = "anx_full_forward_mark_u8" if u8 else "anx_full_forward_mark"
+            else:
+                fn = "anx_full_forward_u8" if u8 else "anx_full_forward"
+            nat.call(fn, self._h, x.data_ptr(), x.shape[0], z.data_ptr(), stream)
+        else:
+            k, idx, prob = head
+            nat.call("anx_full_classify_u8" if u8 else "anx_full_classify", self._h, x.data_ptr(), x.shape[0], k,
+                     idx.data_ptr(), prob.data_ptr(), z.data_ptr() if z is not None else None, stream, int(mark))
+
+    def _run(self, x, z, head, free: bool = False, pre_lane=None, on_lane=None) -> None:
+        """:meth:`_launch` of every lane's slice through :mod:`anx.models.lanes`: forked and joined within the
+        call, or (``free``) left running on the lanes' streams until :meth:`join`."""
+        def run(i, lo, hi, st=None, lead=False):
+            eng = self._lane(i)
+            eng._ensure(hi - lo)
+            eng._launch(x[lo:hi], z[lo:hi] if z is not None else None,
+                        (head[0], head[1][lo:hi], head[2][lo:hi]) if head is not None else None,
+                        st.cuda_stream if st is not None else None, lead)
+            if lead:
+                return lambda s: nat.call("anx_full_wait_mark", eng._h, s.cuda_stream)
+
+        if free:
+            # growing an engine may synchronise the device: before its lane's waits, not between them and the call
+            self._streams.run_free(x.shape[0], run, pre_lane, on_lane,
+                                   prepare=lambda i, lo, hi: self._lane(i)._ensure(hi - lo))
+        else:
+            self._streams.run_joined(x.shape[0], run)
 
     def _check_head(self, x, k, idx, prob):
         """classify's outputs: validated like ``out`` in :meth:`_check`, allocated when not given."""
@@ -270,31 +260,8 @@ class AlexNetFull:
         self._check_x(x)
         z = self._check(x, out[2] if len(out) == 3 else None) if want_logits else None
         idx, prob = self._check_head(x, k, *(out[:2] if out else (None, None)))
-        self._classify(x, k, idx, prob, z)
+        self._run(x, z, (k, idx, prob))
         return (idx, prob, z) if want_logits else (idx, prob)
-
-    def _classify(self, x, k, idx, prob, z):
-        N = x.shape[0]
-        fn = "anx_full_classify_u8" if x.dtype == torch.uint8 else "anx_full_classify"
-        zp = z.data_ptr() if z is not None else None
-        L = 1 + len(self._lanes)
-        if L == 1 or N < L:
-            self._ensure(N)
-            nat.call(fn, self._h, x.data_ptr(), N, k, idx.data_ptr(), prob.data_ptr(), zp,
-                     nat.stream_ptr(self.device), 0)
-            return
-        bounds = [N * i // L for i in range(L + 1)]
-        cur = torch.cuda.current_stream(self.device)
-        for i, st in enumerate(self._lane_streams, start=1):
-            st.wait_stream(cur)  # fork: inputs produced / outputs free on the current stream
-            lo, hi = bounds[i], bounds[i + 1]
-            with torch.cuda.stream(st):
-                self._lanes[i - 1]._classify(x[lo:hi], k, idx[lo:hi], prob[lo:hi], z[lo:hi] if z is not None else None)
-        self._ensure(bounds[1])
-        nat.call(fn, self._h, x.data_ptr(), bounds[1], k, idx.data_ptr(), prob.data_ptr(), zp,
-                 nat.stream_ptr(self.device), 0)
-        for st in self._lane_streams:
-            cur.wait_stream(st)  # join
 
     def classify_async(self, x: torch.Tensor, idx_out: torch.Tensor, prob_out: torch.Tensor, k: int = 5, on_lane=None,
                        pre_lane=None):
@@ -303,63 +270,23 @@ class AlexNetFull:
         writes ``idx_out`` ``[N,k]`` int32 and ``prob_out`` ``[N,k]`` fp32. :meth:`join` before reading them."""
         self._check_x(x)
         idx_out, prob_out = self._check_head(x, k, idx_out, prob_out)
-        N = x.shape[0]
-        L = 1 + len(self._lanes)
-        if L == 1 or N < L or self.device.type != "cuda":
-            if pre_lane is not None:
-                pre_lane(0, 0, N)
-            self._classify(x, k, idx_out, prob_out, None)
-            if on_lane is not None:
-                on_lane(0, 0, N)
-            return idx_out, prob_out
-        if getattr(self, "_own_stream", None) is None:
-            self._own_stream = torch.cuda.Stream(self.device)
-        streams = [self._own_stream, *self._lane_streams]
-        engines = [self, *self._lanes]
-        bounds = self.lane_bounds(N)
-        fresh = all(st.query() for st in streams)
-        cur = torch.cuda.current_stream(self.device)
-        fn = "anx_full_classify_u8" if x.dtype == torch.uint8 else "anx_full_classify"
-        for i, (eng, st) in enumerate(zip(engines, streams)):
-            lo, hi = bounds[i], bounds[i + 1]
-            eng._ensure(hi - lo)
-            if fresh:
-                st.wait_stream(cur)
-                if i > 0:
-                    nat.call("anx_full_wait_mark", engines[i - 1]._h, st.cuda_stream)
-            with torch.cuda.stream(st):
-                if pre_lane is not None:
-                    pre_lane(i, lo, hi)
-                nat.call(fn, eng._h, x[lo:hi].data_ptr(), hi - lo, k, idx_out[lo:hi].data_ptr(),
-                         prob_out[lo:hi].data_ptr(), None, st.cuda_stream, int(fresh and i + 1 < L))
-                if on_lane is not None:
-                    on_lane(i, lo, hi)
+        self._run(x, None, (k, idx_out, prob_out), True, pre_lane, on_lane)
         return idx_out, prob_out
 
     def last_head(self, lane: int = 0) -> str | None:
         """What the head of the last call of this model's engine (``lane`` > 0: that side lane's) read: ``"slabs"``
         (it reduced FC8's split-K slabs itself), ``"logits"`` (logits FC8 or the split-K reduce wrote), ``None`` when
         that call was a plain forward. Recorded at the launch; reading it makes no device call."""
-        if lane:
-            return self._lanes[lane - 1].last_head()
-        buf = C.create_string_buffer(32)
-        nat.call("anx_full_last_head", self._h, buf, len(buf))
-        return buf.value.decode() or None
+        return nat.read_str("anx_full_last_head", self._lane(lane)._h, 32)
 
     def lane_bounds(self, n: int) -> list[int]:
         """Image boundaries [0, ..., n] of the lanes :meth:`forward_async` runs ``n`` images on (the
         pipeline's per-lane gather segments; ScatterComputeGather's root shedding needs them)."""
-        L = 1 + len(self._lanes)
-        if L == 1 or n < L or self.device.type != "cuda":
-            return [0, n]
-        return [n * i // L for i in range(L + 1)]
+        return self._streams.bounds(n)
 
     def join(self) -> None:
-        if self.device.type != "cuda":
-            return
-        cur = torch.cuda.current_stream(self.device)
-        for st in [s for s in [getattr(self, "_own_stream", None)] if s is not None] + self._lane_streams:
-            cur.wait_stream(st)
+        """Make the current stream wait for every lane of :meth:`forward_async` / :meth:`classify_async`."""
+        self._streams.join()
 
     TAPS = ((55, 55, 96), (31, 31, 96), (27, 27, 256), (15, 15, 256), (15, 15, 384), (15, 15, 384), (13, 13, 256),
             (9216,), (4096,), (4096,), (57, 57, 48))
@@ -382,12 +309,8 @@ class AlexNetFull:
         "conv5", "fc6" .. "fc8": {"kernel": "big" | "glds" | "staged", "id": wide-tile config | LDS-DMA
         slots | tile variant, "splitk": K slices}}``, ``None`` for a layer that has not run. The engine
         records it where it launches, and reading it makes no device call."""
-        if lane:
-            return self._lanes[lane - 1].last_path()
         import json
-        buf = C.create_string_buffer(1024)
-        nat.call("anx_full_last_path", self._h, buf, len(buf))
-        return json.loads(buf.value.decode())
+        return json.loads(nat.read_str("anx_full_last_path", self._lane(lane)._h, 1024))
 
 
 def reference_forward(x: torch.Tensor, w: dict, groups2: int = 1, lrn_mode: str = "div_n",

@@ -361,14 +361,16 @@ def test_stream_lanes_bit_identical(cuda, lanes, N):
     assert N >= lanes * LANE_MIN or torch.equal(many(x), ref2)
 
 
-@pytest.mark.parametrize("N", [128, 300])
-def test_forward_async_lanes_bit_identical(cuda, N):
+@pytest.mark.parametrize("N,stagger", [(128, False), (300, False), (32, True)])
+def test_forward_async_lanes_bit_identical(cuda, N, stagger):
     """forward_async (the bench's dp step: free-running lanes, no per-call join, lanes started half a
     forward apart when idle) computes exactly the one-lane forward, over repeated calls on the same
-    buffers, after a device synchronisation (fresh start again), with per-lane hooks in order."""
+    buffers, after a device synchronisation (fresh start again), with per-lane hooks in order. 32 images
+    (2 * LANE_MIN, the smallest batch that splits) with ``stagger``: lane 0 runs stage 1, event, stage 2."""
     x = init_input(N, "rand", seed=31).to(cuda)
     one = AlexNetBlocks(device=cuda, init="rand", seed=31, max_batch=N)
     many = AlexNetBlocks(one.weights, device=cuda, max_batch=N, lanes=2)
+    many.stagger = stagger
     ref = one(x).clone()
     y = torch.full_like(ref, float("nan"))
     seen = []
