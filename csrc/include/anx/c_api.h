@@ -100,6 +100,22 @@ int anx_softmax_topk(const float* src, int ksplit, size_t slab_stride, const flo
                      int* idx, float* prob, float* logits_out, void* stream);
 int anx_cpu_softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k,
                          int* idx, float* prob, float* logits_out);
+/* Antialiased resize + crop of byte images (cpu::resize_crop_u8 in anx/ops.hpp is the definition; the device form
+   writes the same bytes). Image i: H x W x 3 bytes HWC at ptr, rows `pitch` bytes apart (>= 3W), any byte address;
+   its box: origin (y0h, x0h) in HALF pixels, bh x bw pixels, inside the image. out: n x OH x OW x 3 bytes, any byte
+   address. Limits: 1 <= OH, OW <= 512, 1 <= H, W <= 16384, bh <= 16 OH, bw <= 16 OW. The device form takes the
+   descriptors twice: descs_device (device memory, read by the kernel) and descs_host, the caller's host copy of
+   the same n descriptors. Every limit is checked on the host copy before anything is launched, so the kernel
+   never runs on an unvalidated box; a missed limit returns nonzero and touches no memory. */
+typedef struct anx_image_desc {
+  const uint8_t* ptr;
+  int H, W;
+  int64_t pitch;
+  int y0h, x0h, bh, bw;
+} anx_image_desc;
+int anx_resize_crop_u8(const anx_image_desc* descs_device, const anx_image_desc* descs_host, int n, uint8_t* out,
+                       int OH, int OW, void* stream);
+int anx_cpu_resize_crop_u8(const anx_image_desc* descs_host, int n, uint8_t* out, int OH, int OW);
 /* conv2 input window geometry: pointer of (image n, pool1 row r), row stride and image stride (floats). */
 int anx_engine_window(void* e, const anx_tile_c* t, int n, int r, float** ptr, size_t* row_floats,
                       size_t* image_floats);

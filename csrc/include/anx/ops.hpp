@@ -49,6 +49,31 @@ void softmax_topk(const float* src, int ksplit, size_t slab_stride, const float*
                   float* prob, float* logits_out);
 }  // namespace cpu
 
+// One source image of resize_crop_u8: H x W x 3 bytes, HWC, rows `pitch` bytes apart (pitch >= 3W), from any byte
+// address; and its box in its own pixels: origin (y0h, x0h) in HALF pixels (a centred crop of odd slack is exact),
+// size bh x bw pixels, inside the image.
+struct ImageDesc {
+  const uint8_t* ptr;
+  int H, W;
+  int64_t pitch;
+  int y0h, x0h, bh, bw;
+};
+// The limits of resize_crop_u8, checked before any memory is touched: 1 <= OH, OW <= 512; per image a pointer,
+// 1 <= H, W <= 16384, pitch >= 3W, bh, bw >= 1, 0 <= y0h, y0h + 2 bh <= 2H (likewise x), bh <= 16 OH, bw <= 16 OW.
+// Returns null when all n descriptors pass, else a static message naming the first limit missed.
+const char* resize_crop_check(const ImageDesc* d, int n, int OH, int OW);
+
+namespace cpu {
+// Antialiased resize + crop of byte images: image i's box resampled onto out[i] (OH x OW x 3 bytes, images
+// contiguous) with torch / PIL's antialiased bilinear (triangle) filter in fixed point, horizontal pass first.
+// THE definition of the operation (hip::resize_crop_u8 computes the same bytes). With the per-axis 15-bit tap
+// weights q of anx/resize_taps.hpp:
+//   h[y][ox][c]     = (sum_j q^x_j src[y][j][c] + 64) >> 7          (16 bits, at most 65280)
+//   out[oy][ox][c]  = (sum_y q^y_y h[y][ox][c] + 2^22) >> 23        (in [0, 255] without a clamp)
+// The descriptors must have passed resize_crop_check. The reference has no resampling: its programs fill floats.
+void resize_crop_u8(const ImageDesc* d, int n, uint8_t* out, int OH, int OW);
+}  // namespace cpu
+
 // ----------------------------------------------------------------------------------------
 // HIP launchers. All take device pointers and a stream; none allocate or synchronise
 // (safe under hipGraph capture). Return hipSuccess or the launch error.
@@ -198,6 +223,15 @@ hipError_t conv1_fused_u8(const Conv1WinoPlan& w, const uint8_t* x, const U8Norm
 hipError_t conv1_fused_pool_u8(const Conv1WinoPlan& w, const uint8_t* x, const U8Norm& nm, const float* U,
                                const float* bias, OutView window, float* p1, int Hp, int Wp, bool relu, hipStream_t s,
                                int um = 0);
+
+// Antialiased resize + crop of a batch of byte images of different sizes in one launch (resize_crop_u8.hip;
+// cpu::resize_crop_u8 is the definition, and the kernel writes the same bytes). `dev` holds the n descriptors in
+// device memory (their ptr fields device addresses); `host` is the caller's host copy of the same descriptors: the
+// launcher checks every limit on it (resize_crop_check) and sizes the kernel's LDS from it, so the kernel never
+// runs on an unvalidated box. Returns hipErrorInvalidValue for a missed limit or a null pointer; n == 0 launches
+// nothing. out: n x OH x OW x 3 bytes, from any byte address.
+hipError_t resize_crop_u8(const ImageDesc* dev, const ImageDesc* host, int n, uint8_t* out, int OH, int OW,
+                          hipStream_t s);
 
 // The classifier head (softmax_topk.hip; cpu::softmax_topk is the definition): one workgroup per row reduces the
 // split-K slabs (+ bias) once, keeps the row in LDS, and writes the k best classes and their softmax probabilities;

@@ -124,7 +124,8 @@ const char* anx_last_error(void) { return g_err.c_str(); }
 // 4: device-owner diagnostics (anx_device_live, anx_device_fail_alloc)
 // 5: the classifier head (anx_softmax_topk, anx_cpu_softmax_topk, anx_full_classify, anx_full_classify_u8,
 //    anx_full_last_head; knob bf16_head)
-int anx_abi_version(void) { return 5; }
+// 6: antialiased resize + crop of byte images (anx_resize_crop_u8, anx_cpu_resize_crop_u8, anx_image_desc)
+int anx_abi_version(void) { return 6; }
 
 int anx_device_live(size_t out[4]) {
   if (!out) return fail("anx_device_live: no buffer");
@@ -335,6 +336,33 @@ int anx_cpu_softmax_topk(const float* src, int ksplit, size_t slab_stride, const
   return guarded("anx_cpu_softmax_topk", [&] {
     if (softmax_topk_args("anx_cpu_softmax_topk", src, ksplit, M, K, k, idx, prob)) return 1;
     anx::cpu::softmax_topk(src, ksplit, slab_stride, bias, M, K, k, idx, prob, logits_out);
+    return 0;
+  });
+}
+
+static_assert(sizeof(anx_image_desc) == sizeof(anx::ImageDesc) && sizeof(anx_image_desc) == 40,
+              "anx_image_desc is anx::ImageDesc");
+
+int anx_resize_crop_u8(const anx_image_desc* descs_device, const anx_image_desc* descs_host, int n, uint8_t* out,
+                       int OH, int OW, void* stream) {
+  return guarded("anx_resize_crop_u8", [&] {
+    const auto* host = reinterpret_cast<const anx::ImageDesc*>(descs_host);
+    if (n < 0 || (n > 0 && (!descs_device || !descs_host || !out)))
+      return fail("anx_resize_crop_u8: null descriptors or output");
+    if (const char* why = anx::resize_crop_check(host, n, OH, OW)) return fail(std::string("anx_resize_crop_u8: ") + why);
+    return hip_status(anx::hip::resize_crop_u8(reinterpret_cast<const anx::ImageDesc*>(descs_device), host, n, out, OH,
+                                               OW, S(stream)),
+                      "anx_resize_crop_u8");
+  });
+}
+
+int anx_cpu_resize_crop_u8(const anx_image_desc* descs_host, int n, uint8_t* out, int OH, int OW) {
+  return guarded("anx_cpu_resize_crop_u8", [&] {
+    const auto* host = reinterpret_cast<const anx::ImageDesc*>(descs_host);
+    if (n < 0 || (n > 0 && (!descs_host || !out))) return fail("anx_cpu_resize_crop_u8: null descriptors or output");
+    if (const char* why = anx::resize_crop_check(host, n, OH, OW))
+      return fail(std::string("anx_cpu_resize_crop_u8: ") + why);
+    anx::cpu::resize_crop_u8(host, n, out, OH, OW);
     return 0;
   });
 }

@@ -85,6 +85,8 @@ _SIGS = {
     "anx_cpu_decode_u8": (_I, [_P, _P, _SZ, _I, _P, _P]),
     "anx_softmax_topk": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _P, _P, _P, _P]),
     "anx_cpu_softmax_topk": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _P, _P, _P]),
+    "anx_resize_crop_u8": (_I, [_P, _P, _I, _P, _I, _I, _P]),
+    "anx_cpu_resize_crop_u8": (_I, [_P, _I, _P, _I, _I]),
     "anx_cpu_engine_set_input_norm": (_I, [_P, _P, _P]),
     "anx_cpu_engine_forward_u8": (_I, [_P, _P, _I, _P]),
     "anx_cpu_engine_tile_forward_u8": (_I, [_P, _P, _I, C.POINTER(TileC), _P]),

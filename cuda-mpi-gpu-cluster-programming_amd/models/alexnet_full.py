@@ -14,6 +14,10 @@ bit. With the default Conv1 (``bf16_conv1`` 2) and knob ``bf16_u8=1`` the row-ba
 (``last_input() == "u8_ring"``, no float copy of the input on the device); everywhere else the launch chunk is
 decoded into a workspace that the first such forward allocates (``"u8_decode"``: warm up once before capturing a
 graph) and the float kernels run on it.
+
+Byte images of any other size go through :meth:`AlexNetFull.forward_images` / :meth:`AlexNetFull.classify_images`:
+one :func:`anx.ops.resize_crop_u8` launch (antialiased resize + centre crop, integer arithmetic) into a byte workspace
+of the model, then the byte path above.
 """
 from __future__ import annotations
 
@@ -70,6 +74,7 @@ class AlexNetFull:
             raise ValueError("the bf16 full-AlexNet engine is GPU-only (use reference_forward on the CPU)")
         self._h = None
         self._cap = 0
+        self._img_ws, self._img_cap = None, 0  # byte workspace of forward_images / classify_images (lane 0's model)
         self.input_norm = input_norm
         self._norm = norm_scale_offset(input_norm, 3)
         if lanes < 1:
@@ -262,6 +267,37 @@ class AlexNetFull:
         idx, prob = self._check_head(x, k, *(out[:2] if out else (None, None)))
         self._run(x, z, (k, idx, prob))
         return (idx, prob, z) if want_logits else (idx, prob)
+
+    def _preprocess(self, images, resize) -> torch.Tensor:
+        """``images`` (as :func:`anx.ops.resize_crop_u8` takes them) -> ``uint8 [N,227,227,3]`` in the model-owned
+        byte workspace, by one :func:`anx.ops.resize_crop_u8` launch on the current stream (``center_box`` boxes)."""
+        from ..ops import resize_crop_u8
+        n = images.shape[0] if isinstance(images, torch.Tensor) else len(images)
+        for im in ((images,) if isinstance(images, torch.Tensor) else images):
+            if isinstance(im, torch.Tensor) and im.device != self.device:
+                raise ValueError(f"expected images on {self.device}, got one on {im.device}")
+        if self._img_ws is None or n > self._img_cap:
+            # the old workspace goes back to torch's allocator, which hands it out again in stream order
+            self._img_cap = max(1, n)
+            self._img_ws = torch.empty((self._img_cap, 227, 227, 3), device=self.device, dtype=torch.uint8)
+        return resize_crop_u8(images, 227, resize, out=self._img_ws[:n])
+
+    def forward_images(self, images, out: torch.Tensor | None = None, resize: int | None = 256) -> torch.Tensor:
+        """Byte images of any size -> logits ``[N, classes]``: ``images`` is a list of ``uint8 [H,W,3]`` tensors (each
+        its own size) or one ``[N,H,W,3]`` tensor on the model's device. Each image is resized and centre-cropped to
+        227 x 227 ("shorter side to ``resize``, centre crop 227": :func:`anx.ops.center_box`; ``resize=None``
+        resamples the whole image) by :func:`anx.ops.resize_crop_u8`, one kernel for the batch, into a byte
+        workspace the model owns; then the byte forward runs on it, so lanes, ``input_norm``, :meth:`last_input`
+        (``"u8_ring"`` by default) and :meth:`last_head` mean what they mean for :meth:`forward`. The result equals
+        ``forward(anx.ops.resize_crop_u8(images, 227, resize))`` bit for bit. The workspace grows to the largest
+        batch seen, like the engine itself, and each call copies its image descriptors to the device: call once with
+        the largest batch before capturing a graph, as for the ``"u8_decode"`` workspace."""
+        return self.forward(self._preprocess(images, resize), out)
+
+    def classify_images(self, images, k: int = 5, resize: int | None = 256, return_logits: bool = False):
+        """:meth:`classify` of byte images of any size (``images``, ``resize`` and the workspace as in
+        :meth:`forward_images`): equal bit for bit to ``classify(anx.ops.resize_crop_u8(images, 227, resize), k)``."""
+        return self.classify(self._preprocess(images, resize), k, return_logits=return_logits)
 
     def classify_async(self, x: torch.Tensor, idx_out: torch.Tensor, prob_out: torch.Tensor, k: int = 5, on_lane=None,
                        pre_lane=None):

@@ -26,13 +26,15 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
 from .. import _native as nat
 from ..config import conv_out_dim, pool_out_dim
 
-__all__ = ["conv2d", "relu", "maxpool", "lrn", "maxpool_lrn", "decode_u8", "softmax_topk", "clear_cache"]
+__all__ = ["conv2d", "relu", "maxpool", "lrn", "maxpool_lrn", "decode_u8", "softmax_topk", "resize_crop_u8",
+           "center_box", "clear_cache"]
 
 _LRN_MODES = {"div_n": 0, "raw": 1}
 _pack_cache: dict = {}
@@ -134,6 +136,146 @@ def decode_u8(x: torch.Tensor, scale=None, offset=None) -> torch.Tensor:
     else:
         nat.call("anx_cpu_decode_u8", x.data_ptr(), y.data_ptr(), x.numel(), sc.numel(), sc.data_ptr(), of.data_ptr())
     return y
+
+
+RESIZE_MAX_IN, RESIZE_MAX_OUT, RESIZE_MAX_SCALE = 16384, 512, 16  # kResizeMax* (anx/resize_taps.hpp)
+_IMAGE_DESC = np.dtype([("ptr", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pitch", "<i8"), ("y0h", "<i4"), ("x0h", "<i4"),
+                        ("bh", "<i4"), ("bw", "<i4")])  # anx::ImageDesc / anx_image_desc: 40 bytes
+
+
+def _size2(size) -> tuple[int, int]:
+    oh, ow = (size, size) if isinstance(size, int) else tuple(size)
+    return int(oh), int(ow)
+
+
+def center_box(H: int, W: int, resize: int | None = 256, size=227) -> tuple[int, int, int, int]:
+    """The usual "shorter side to ``resize``, centre crop ``size``" box of an ``H x W`` image, in the image's own
+    pixels, as :func:`resize_crop_u8` takes it: ``(y0h, x0h, bh, bw)`` with the origin in HALF pixels (so a centred
+    crop of odd slack is exact). ``b = max(1, round(size * min(H, W) / resize))`` (halves round up), clipped to
+    ``min(H, W)``; ``y0h = H - bh``, ``x0h = W - bw``. ``size`` ``(OH, OW)`` gives a box of that aspect.
+    ``resize=None``: the whole image, ``(0, 0, H, W)``."""
+    if resize is None:
+        return (0, 0, int(H), int(W))
+    m = min(H, W)
+    bh, bw = (min(m, max(1, (2 * s * m + resize) // (2 * resize))) for s in _size2(size))
+    return (int(H - bh), int(W - bw), int(bh), int(bw))
+
+
+def _image_geometry(images):
+    """int64 [n, 4] rows (data pointer, H, W, row pitch in bytes) of a list of uint8 [H,W,3] tensors or one
+    [N,H,W,3] tensor, and their device (None for an empty list); layouts the kernels cannot read raise."""
+    bad_layout = "resize_crop_u8: the last two dims of an image must be contiguous, rows >= 3W bytes apart"
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4 or images.dtype != torch.uint8 or images.shape[3] != 3:
+            raise ValueError("resize_crop_u8: a tensor of images must be uint8 [N,H,W,3]")
+        N, H, W, _ = images.shape
+        st = images.stride()
+        pitch = st[1] if H > 1 else max(st[1], 3 * W)
+        if (W > 1 and st[2] != 3) or st[3] != 1 or pitch < 3 * W or (N > 1 and st[0] < 0):
+            raise ValueError(bad_layout)
+        geo = np.empty((N, 4), dtype=np.int64)
+        geo[:, 0] = images.data_ptr() + np.arange(N, dtype=np.int64) * st[0]
+        geo[:, 1:] = (H, W, pitch)
+        return geo, images.device
+    rows, dev = [], None
+    for im in images:
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+            raise ValueError("resize_crop_u8: every image must be a uint8 [H,W,3] tensor")
+        if dev is None:
+            dev = im.device
+        elif im.device != dev:
+            raise ValueError("resize_crop_u8: all images must be on one device")
+        H, W, _ = im.shape
+        st = im.stride()
+        pitch = st[0] if H > 1 else max(st[0], 3 * W)
+        if (W > 1 and st[1] != 3) or st[2] != 1 or pitch < 3 * W:
+            raise ValueError(bad_layout)
+        rows.append((im.data_ptr(), H, W, pitch))
+    return np.array(rows, dtype=np.int64).reshape(len(rows), 4), dev
+
+
+def _image_descs(geo, OH: int, OW: int, resize, boxes):
+    """The anx::ImageDesc array of images ``geo`` (:func:`_image_geometry`) with ``boxes`` (default
+    :func:`center_box`), every limit of the operation checked: a miss is a ValueError naming the image."""
+    n = geo.shape[0]
+    H, W = geo[:, 1], geo[:, 2]
+    if n and not (H.min() >= 1 and W.min() >= 1 and H.max() <= RESIZE_MAX_IN and W.max() <= RESIZE_MAX_IN):
+        raise ValueError(f"resize_crop_u8: image sizes must be 1 .. {RESIZE_MAX_IN}")
+    if boxes is None:
+        if resize is None:
+            box = np.stack([np.zeros_like(H), np.zeros_like(H), H, W], axis=1)
+        else:  # center_box, for all images at once
+            m = np.minimum(H, W)
+            bh, bw = (np.minimum(m, np.maximum(1, (2 * s * m + resize) // (2 * resize))) for s in (OH, OW))
+            box = np.stack([H - bh, W - bw, bh, bw], axis=1)
+    else:
+        try:
+            box = np.array([[int(v) for v in b] for b in boxes], dtype=np.int64).reshape(len(boxes), 4)
+        except (TypeError, ValueError) as e:
+            raise ValueError("resize_crop_u8: a box is four integers (y0h, x0h, bh, bw)") from e
+        if box.shape[0] != n:
+            raise ValueError("resize_crop_u8: one box per image")
+    y0h, x0h, bh, bw = box.T
+    outside = (bh < 1) | (bw < 1) | (y0h < 0) | (x0h < 0) | (y0h + 2 * bh > 2 * H) | (x0h + 2 * bw > 2 * W)
+    if outside.any():
+        i = int(np.argmax(outside))
+        raise ValueError(f"resize_crop_u8: box {tuple(int(v) for v in box[i])} (half-pixel origin) is not inside image "
+                         f"{i} of {(int(H[i]), int(W[i]))}")
+    big = (bh > RESIZE_MAX_SCALE * OH) | (bw > RESIZE_MAX_SCALE * OW)
+    if big.any():
+        i = int(np.argmax(big))
+        raise ValueError(f"resize_crop_u8: box {(int(bh[i]), int(bw[i]))} of image {i} is more than {RESIZE_MAX_SCALE} "
+                         f"times the output {(OH, OW)}")
+    desc = np.zeros(n, dtype=_IMAGE_DESC)
+    for k, col in zip(("ptr", "H", "W", "pitch"), geo.T):
+        desc[k] = col
+    for k, col in zip(("y0h", "x0h", "bh", "bw"), box.T):
+        desc[k] = col
+    return desc
+
+
+def resize_crop_u8(images, size=227, resize: int | None = 256, boxes=None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Byte images of any size -> ``uint8 [N, OH, OW, 3]``: each image's box resampled onto the output with torch /
+    PIL's antialiased bilinear (triangle) filter, in fixed point, one native kernel for the whole batch.
+
+    ``images``: a list of ``uint8 [H,W,3]`` tensors (each its own size) or one ``[N,H,W,3]`` tensor, all on one
+    device; the last two dims contiguous, the row stride free (a column slice of a bigger image is fine).
+    ``size``: ``OH = OW`` or ``(OH, OW)``, 1 to 512. ``boxes``: one ``(y0h, x0h, bh, bw)`` per image (origin in half
+    pixels, size in pixels, inside the image, at most 16 times the output per axis); default
+    :func:`center_box` ``(H, W, resize, size)``. ``out``: a contiguous ``uint8 [N,OH,OW,3]`` tensor on the images'
+    device to write into (any byte offset). A missed limit is a ``ValueError``.
+
+    The definition is the host function ``cpu::resize_crop_u8`` (CPU tensors run it): per axis 15-bit tap weights
+    ``q`` summing to exactly 2^15 (``anx/resize_taps.hpp``), horizontal pass first into 16 bits,
+    ``h = (sum q_x * src + 64) >> 7``, then ``out = (sum q_y * h + 2^22) >> 23``. GPU tensors run the gfx950 kernel
+    on torch's current stream; it computes the same integers, so the bytes are equal. The descriptors (pointer,
+    size, pitch, box per image) are built on the host, checked there natively, and copied to the device with the
+    stream. The reference has no resampling stage."""
+    OH, OW = _size2(size)
+    if not (1 <= OH <= RESIZE_MAX_OUT and 1 <= OW <= RESIZE_MAX_OUT):
+        raise ValueError(f"resize_crop_u8: output size must be 1 .. {RESIZE_MAX_OUT}, got {(OH, OW)}")
+    geo, dev = _image_geometry(images)
+    n = geo.shape[0]
+    if dev is None:
+        dev = out.device if out is not None else torch.device("cpu")
+    desc = _image_descs(geo, OH, OW, resize, boxes)
+    shape = (n, OH, OW, 3)
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.uint8)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"resize_crop_u8: out must be a contiguous uint8 {shape} tensor on {dev}, got "
+                         f"{tuple(out.shape)} {out.dtype} on {out.device}")
+    if n == 0:
+        return out
+    host = torch.from_numpy(desc.view(np.uint8))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            ddev = host.to(dev, non_blocking=True)  # on the current stream, ahead of the kernel
+            nat.call("anx_resize_crop_u8", ddev.data_ptr(), host.data_ptr(), n, out.data_ptr(), OH, OW,
+                     nat.stream_ptr(dev))
+    else:
+        nat.call("anx_cpu_resize_crop_u8", host.data_ptr(), n, out.data_ptr(), OH, OW)
+    return out
 
 
 MAX_TOPK = 16          # kMaxTopK (anx/ops.hpp)
