@@ -170,6 +170,18 @@ class FullEngine {
                       bool mark = false);
   hipError_t classify_u8(const uint8_t* x, int N, int k, int* idx, float* prob, float* logits, hipStream_t s,
                          bool mark = false);
+  // classify over V views per image: x holds `rows` = N * V images, image-major (row i * V + v is view v of image
+  // i); idx / prob are [rows / V][k], the k best classes of the mean of each image's V softmax rows
+  // (cpu::softmax_topk_views is the definition); logits (nullable): [rows, classes]. The layer chain, mark,
+  // last_input(), last_path() and last_head() are classify's: where FC8 ends in split-K slabs the view kernel takes
+  // them with the bias (Knobs::bf16_head), else it runs on the written logits. A launch chunk holds whole images
+  // (the chunk step is the largest multiple of V images the engine's chunk holds). hipErrorInvalidValue: V outside
+  // 1 .. kMaxViews, rows % V != 0, a chunk smaller than V, more than hip::kSoftmaxViewsMaxK classes, k as
+  // classify. No call allocates.
+  hipError_t classify_views(const float* x, int rows, int V, int k, int* idx, float* prob, float* logits, hipStream_t s,
+                            bool mark = false);
+  hipError_t classify_views_u8(const uint8_t* x, int rows, int V, int k, int* idx, float* prob, float* logits,
+                               hipStream_t s, bool mark = false);
   // What the head of the last call read: "slabs" (it reduced FC8's split-K slabs), "logits" (written logits), null
   // when the last call was forward / forward_u8. Recorded at the launch from host state.
   const char* last_head() const { return head_; }
@@ -210,6 +222,7 @@ class FullEngine {
     float* prob;
     float* logits;  // nullable
     bool slabs;
+    int views = 0;  // classify_views: rows per image (idx / prob then hold one row per image); 0: one row per image
   };
   hipError_t conv(Layer& L, int N, int Hp, int Wp, const void* x, hip::OutViewB out, float* out_f32, bool relu,
                   hipStream_t s, Head* head = nullptr);

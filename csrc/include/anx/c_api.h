@@ -116,6 +116,26 @@ typedef struct anx_image_desc {
 int anx_resize_crop_u8(const anx_image_desc* descs_device, const anx_image_desc* descs_host, int n, uint8_t* out,
                        int OH, int OW, void* stream);
 int anx_cpu_resize_crop_u8(const anx_image_desc* descs_host, int n, uint8_t* out, int OH, int OW);
+/* The same with mirrored outputs: one flag byte per output; a nonzero flag gives the unflipped output of the same
+   descriptor with its columns reversed, out[oy][OW-1-ox][c]. Descriptors may share a source image (views). The
+   device form takes the flags like the descriptors, as a device copy and the caller's host copy: both null is the
+   entry point above, byte for byte; one null and the other not is refused. */
+int anx_resize_crop_u8_flip(const anx_image_desc* descs_device, const anx_image_desc* descs_host,
+                            const uint8_t* flips_device, const uint8_t* flips_host, int n, uint8_t* out, int OH, int OW,
+                            void* stream);
+int anx_cpu_resize_crop_u8_flip(const anx_image_desc* descs_host, const uint8_t* flips_host, int n, uint8_t* out, int OH,
+                                int OW);
+/* The view-averaging head: rows [N*V][K], image-major (row i*V + v is view v of image i), reduced from slabs (+ bias)
+   like anx_softmax_topk's. p_v = softmax of view v's row (anx_softmax_topk's expressions); pbar[c] = ((p_0[c] +
+   p_1[c]) + ... + p_{V-1}[c]) / (float)V in fp32; idx [N][k] = the k best classes by pbar descending then index
+   ascending, prob [N][k] = pbar there; probs_out (nullable) [N][K] = pbar; logits_out (nullable) [N*V][K] = the
+   reduced rows. 1 <= V <= 32, 1 <= k <= min(K, 16); on the device K <= 7680 (two rows in LDS). The ranking is by
+   probability: with V = 1, classes whose probabilities underflow to one value tie (lower index first) where
+   anx_softmax_topk orders them by logit. */
+int anx_softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K,
+                           int k, int* idx, float* prob, float* probs_out, float* logits_out, void* stream);
+int anx_cpu_softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K,
+                               int k, int* idx, float* prob, float* probs_out, float* logits_out);
 /* conv2 input window geometry: pointer of (image n, pool1 row r), row stride and image stride (floats). */
 int anx_engine_window(void* e, const anx_tile_c* t, int n, int r, float** ptr, size_t* row_floats,
                       size_t* image_floats);
@@ -153,6 +173,14 @@ int anx_full_classify(void* e, const float* x, int N, int k, int* idx, float* pr
 int anx_full_classify_u8(void* e, const uint8_t* x, int N, int k, int* idx, float* prob, float* logits, void* stream,
                          int mark);
 int anx_full_last_head(void* e, char* buf, size_t cap);
+/* classify over V views per image: x holds rows = N*V images, image-major; idx / prob are [rows/V][k], the head is
+   anx_softmax_topk_views (on FC8's slabs with knob bf16_head = 1, as above); logits (nullable) [rows][classes].
+   rows % V == 0, 1 <= V <= 32, classes <= 7680. A launch chunk holds whole images; an engine whose chunk is
+   smaller than V refuses the call. No call allocates. */
+int anx_full_classify_views(void* e, const float* x, int rows, int V, int k, int* idx, float* prob, float* logits,
+                            void* stream, int mark);
+int anx_full_classify_views_u8(void* e, const uint8_t* x, int rows, int V, int k, int* idx, float* prob, float* logits,
+                               void* stream, int mark);
 
 /* ---- host engine (same contract as the device engine; V1 / V2 CPU ranks) ---- */
 int anx_cpu_engine_create(void** out, const anx_block_c* b1, const anx_block_c* b2, int H, int W, const float* w1,

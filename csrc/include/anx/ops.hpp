@@ -47,6 +47,20 @@ void decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, 
 constexpr int kMaxTopK = 16;
 void softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k, int* idx,
                   float* prob, float* logits_out);
+// The view-averaging head: N images of V views each, rows [N * V][K] image-major (row i * V + v is view v of image
+// i). THE definition of hip::softmax_topk_views. Per row, z is reduced as in softmax_topk and
+//   p_v[c]  = exp(z[c] - max) / sum_c exp(z[c] - max)           (softmax_topk's expressions, fp32)
+// per image
+//   pbar[c] = ((p_0[c] + p_1[c]) + ... + p_{V-1}[c]) / float(V)  (fp32, adding in view order)
+//   idx[j]  = the k best classes by pbar descending, then index ascending (a NaN ranks with -inf)
+//   prob[j] = pbar[idx[j]].
+// The ranking is by probability, not by logit: with V = 1 the probabilities are softmax_topk's bits, but classes whose
+// probabilities underflow to the same value tie here and go to the lower index, where softmax_topk still tells
+// their logits apart. 1 <= V <= kMaxViews, 1 <= k <= min(K, kMaxTopK). idx int32 [N][k], prob [N][k], probs_out
+// (nullable) [N][K] = pbar, logits_out (nullable) [N * V][K] = the bits of z. The reference has no classifier head.
+constexpr int kMaxViews = 32;
+void softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K, int k,
+                        int* idx, float* prob, float* probs_out, float* logits_out);
 }  // namespace cpu
 
 // One source image of resize_crop_u8: H x W x 3 bytes, HWC, rows `pitch` bytes apart (pitch >= 3W), from any byte
@@ -72,6 +86,10 @@ namespace cpu {
 //   out[oy][ox][c]  = (sum_y q^y_y h[y][ox][c] + 2^22) >> 23        (in [0, 255] without a clamp)
 // The descriptors must have passed resize_crop_check. The reference has no resampling: its programs fill floats.
 void resize_crop_u8(const ImageDesc* d, int n, uint8_t* out, int OH, int OW);
+// The same with mirrored outputs: flip (nullable: none) holds one byte per output, and an output whose byte is
+// nonzero is the unflipped output of its descriptor with the columns reversed, out[oy][OW - 1 - ox][c]. Taps,
+// rounding and limits are untouched. Descriptors may name the same image more than once (views of one source).
+void resize_crop_u8(const ImageDesc* d, const uint8_t* flip, int n, uint8_t* out, int OH, int OW);
 }  // namespace cpu
 
 // ----------------------------------------------------------------------------------------
@@ -232,6 +250,13 @@ hipError_t conv1_fused_pool_u8(const Conv1WinoPlan& w, const uint8_t* x, const U
 // nothing. out: n x OH x OW x 3 bytes, from any byte address.
 hipError_t resize_crop_u8(const ImageDesc* dev, const ImageDesc* host, int n, uint8_t* out, int OH, int OW,
                           hipStream_t s);
+// The same with mirrored outputs (the flip overload of cpu::resize_crop_u8 is the definition): one flag byte per
+// output, carried like the descriptors as a device copy the kernel reads and the caller's host copy. Both null: the
+// call above, byte for byte (and the same kernel); one null and the other not: hipErrorInvalidValue. The flag is
+// uniform over a workgroup and only moves the bytes where the band is assembled in LDS, so resampling, staging and the
+// 16-B stores are shared.
+hipError_t resize_crop_u8(const ImageDesc* dev, const ImageDesc* host, const uint8_t* flip_dev, const uint8_t* flip_host,
+                          int n, uint8_t* out, int OH, int OW, hipStream_t s);
 
 // The classifier head (softmax_topk.hip; cpu::softmax_topk is the definition): one workgroup per row reduces the
 // split-K slabs (+ bias) once, keeps the row in LDS, and writes the k best classes and their softmax probabilities;
@@ -242,6 +267,17 @@ hipError_t resize_crop_u8(const ImageDesc* dev, const ImageDesc* host, int n, ui
 constexpr int kSoftmaxTopkLdsRow = 15 * 1024;
 hipError_t softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k,
                         int* idx, float* prob, float* logits_out, hipStream_t s);
+// The view-averaging head (softmax_topk_views.hip; cpu::softmax_topk_views is the definition): one workgroup per
+// image keeps a view's reduced row and the running sum of the views' softmax rows in LDS, loops over the image's V
+// consecutive rows (each reduced from slabs (+ bias) or read as logits, as above), divides by V and ranks the mean.
+// probs_out (nullable) [N][K] receives the mean row, logits_out (nullable) [N * V][K] the reduced rows. Two rows must
+// fit the LDS: K <= kSoftmaxViewsMaxK; that, V outside 1 .. cpu::kMaxViews, k outside 1 .. min(K, kMaxTopK) and null
+// src / idx / prob return hipErrorInvalidValue. N == 0 launches nothing. expf is the device's, so the probabilities
+// are held to fp64 like the host definition's, not to the host's bits; an image's result depends only on the bits
+// of its rows' z, on V and on K.
+constexpr int kSoftmaxViewsMaxK = 7680;
+hipError_t softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K,
+                              int k, int* idx, float* prob, float* probs_out, float* logits_out, hipStream_t s);
 
 // The fused Winograd GEMM + output transform (wino_gemm.hip). V [P][points][C], U [points][K][C/groups]
 // (row = filter), bias + optional ReLU, NHWC store through `out` (Cb, c_off multiples of 4). P tiles of

@@ -125,7 +125,10 @@ const char* anx_last_error(void) { return g_err.c_str(); }
 // 5: the classifier head (anx_softmax_topk, anx_cpu_softmax_topk, anx_full_classify, anx_full_classify_u8,
 //    anx_full_last_head; knob bf16_head)
 // 6: antialiased resize + crop of byte images (anx_resize_crop_u8, anx_cpu_resize_crop_u8, anx_image_desc)
-int anx_abi_version(void) { return 6; }
+// 7: ten views per image: mirrored resize outputs (anx_resize_crop_u8_flip, anx_cpu_resize_crop_u8_flip) and the
+//    view-averaging head (anx_softmax_topk_views, anx_cpu_softmax_topk_views, anx_full_classify_views,
+//    anx_full_classify_views_u8)
+int anx_abi_version(void) { return 7; }
 
 int anx_device_live(size_t out[4]) {
   if (!out) return fail("anx_device_live: no buffer");
@@ -340,6 +343,30 @@ int anx_cpu_softmax_topk(const float* src, int ksplit, size_t slab_stride, const
   });
 }
 
+int anx_softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K,
+                           int k, int* idx, float* prob, float* probs_out, float* logits_out, void* stream) {
+  return guarded("anx_softmax_topk_views", [&] {
+    if (softmax_topk_args("anx_softmax_topk_views", src, ksplit, N, K, k, idx, prob)) return 1;
+    if (V < 1 || V > anx::cpu::kMaxViews) return fail("anx_softmax_topk_views: 1 <= V <= 32 views");
+    if (K > anx::hip::kSoftmaxViewsMaxK)
+      return fail("anx_softmax_topk_views: more than " + std::to_string(anx::hip::kSoftmaxViewsMaxK) +
+                  " classes (two rows must fit the LDS)");
+    return hip_status(anx::hip::softmax_topk_views(src, ksplit, slab_stride, bias, N, V, K, k, idx, prob, probs_out,
+                                                   logits_out, S(stream)),
+                      "anx_softmax_topk_views");
+  });
+}
+
+int anx_cpu_softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K,
+                               int k, int* idx, float* prob, float* probs_out, float* logits_out) {
+  return guarded("anx_cpu_softmax_topk_views", [&] {
+    if (softmax_topk_args("anx_cpu_softmax_topk_views", src, ksplit, N, K, k, idx, prob)) return 1;
+    if (V < 1 || V > anx::cpu::kMaxViews) return fail("anx_cpu_softmax_topk_views: 1 <= V <= 32 views");
+    anx::cpu::softmax_topk_views(src, ksplit, slab_stride, bias, N, V, K, k, idx, prob, probs_out, logits_out);
+    return 0;
+  });
+}
+
 static_assert(sizeof(anx_image_desc) == sizeof(anx::ImageDesc) && sizeof(anx_image_desc) == 40,
               "anx_image_desc is anx::ImageDesc");
 
@@ -363,6 +390,36 @@ int anx_cpu_resize_crop_u8(const anx_image_desc* descs_host, int n, uint8_t* out
     if (const char* why = anx::resize_crop_check(host, n, OH, OW))
       return fail(std::string("anx_cpu_resize_crop_u8: ") + why);
     anx::cpu::resize_crop_u8(host, n, out, OH, OW);
+    return 0;
+  });
+}
+
+int anx_resize_crop_u8_flip(const anx_image_desc* descs_device, const anx_image_desc* descs_host,
+                            const uint8_t* flips_device, const uint8_t* flips_host, int n, uint8_t* out, int OH, int OW,
+                            void* stream) {
+  return guarded("anx_resize_crop_u8_flip", [&] {
+    const auto* host = reinterpret_cast<const anx::ImageDesc*>(descs_host);
+    if (n < 0 || (n > 0 && (!descs_device || !descs_host || !out)))
+      return fail("anx_resize_crop_u8_flip: null descriptors or output");
+    if ((flips_device == nullptr) != (flips_host == nullptr))
+      return fail("anx_resize_crop_u8_flip: the flags go in as a device copy and a host copy, or not at all");
+    if (const char* why = anx::resize_crop_check(host, n, OH, OW))
+      return fail(std::string("anx_resize_crop_u8_flip: ") + why);
+    return hip_status(anx::hip::resize_crop_u8(reinterpret_cast<const anx::ImageDesc*>(descs_device), host, flips_device,
+                                               flips_host, n, out, OH, OW, S(stream)),
+                      "anx_resize_crop_u8_flip");
+  });
+}
+
+int anx_cpu_resize_crop_u8_flip(const anx_image_desc* descs_host, const uint8_t* flips_host, int n, uint8_t* out, int OH,
+                                int OW) {
+  return guarded("anx_cpu_resize_crop_u8_flip", [&] {
+    const auto* host = reinterpret_cast<const anx::ImageDesc*>(descs_host);
+    if (n < 0 || (n > 0 && (!descs_host || !out)))
+      return fail("anx_cpu_resize_crop_u8_flip: null descriptors or output");
+    if (const char* why = anx::resize_crop_check(host, n, OH, OW))
+      return fail(std::string("anx_cpu_resize_crop_u8_flip: ") + why);
+    anx::cpu::resize_crop_u8(host, flips_host, n, out, OH, OW);
     return 0;
   });
 }

@@ -141,6 +141,40 @@ int anx_full_classify_u8(void* e, const uint8_t* x, int N, int k, int* idx, floa
   });
 }
 
+namespace {
+// what the two classify_views entries check beyond classify_args; 0 = fine
+int views_args(const std::string& fn, void* e, int rows, int V) {
+  if (V < 1 || V > anx::cpu::kMaxViews) return fail(fn + ": 1 <= V <= 32 views, got " + std::to_string(V));
+  if (rows < 0 || rows % V != 0)
+    return fail(fn + ": " + std::to_string(rows) + " rows are no whole number of images of " + std::to_string(V) + " views");
+  if (static_cast<anx::FullEngine*>(e)->classes() > anx::hip::kSoftmaxViewsMaxK)
+    return fail(fn + ": more than " + std::to_string(anx::hip::kSoftmaxViewsMaxK) + " classes");
+  return 0;
+}
+}  // namespace
+
+int anx_full_classify_views(void* e, const float* x, int rows, int V, int k, int* idx, float* prob, float* logits,
+                            void* stream, int mark) {
+  return guarded("anx_full_classify_views", [&] {
+    if (classify_args("anx_full_classify_views", e, x, rows, k, idx, prob)) return 1;
+    if (views_args("anx_full_classify_views", e, rows, V)) return 1;
+    return hip_status(
+        static_cast<anx::FullEngine*>(e)->classify_views(x, rows, V, k, idx, prob, logits, S(stream), mark != 0),
+        "anx_full_classify_views");
+  });
+}
+
+int anx_full_classify_views_u8(void* e, const uint8_t* x, int rows, int V, int k, int* idx, float* prob, float* logits,
+                               void* stream, int mark) {
+  return guarded("anx_full_classify_views_u8", [&] {
+    if (classify_args("anx_full_classify_views_u8", e, x, rows, k, idx, prob)) return 1;
+    if (views_args("anx_full_classify_views_u8", e, rows, V)) return 1;
+    return hip_status(
+        static_cast<anx::FullEngine*>(e)->classify_views_u8(x, rows, V, k, idx, prob, logits, S(stream), mark != 0),
+        "anx_full_classify_views_u8");
+  });
+}
+
 // What the head of the last call read ("" after a plain forward and before the first call). Host state only.
 int anx_full_last_head(void* e, char* buf, size_t cap) {
   return guarded("anx_full_last_head", [&] {

@@ -41,6 +41,10 @@ struct Axis {
 }  // namespace
 
 void resize_crop_u8(const ImageDesc* d, int n, uint8_t* out, int OH, int OW) {
+  resize_crop_u8(d, nullptr, n, out, OH, OW);
+}
+
+void resize_crop_u8(const ImageDesc* d, const uint8_t* flip, int n, uint8_t* out, int OH, int OW) {
   const size_t row = static_cast<size_t>(OW) * 3;
   std::vector<uint16_t> h;
   for (int i = 0; i < n; ++i) {
@@ -66,13 +70,16 @@ void resize_crop_u8(const ImageDesc* d, int n, uint8_t* out, int OH, int OW) {
       }
     }
     uint8_t* o = out + static_cast<size_t>(i) * OH * row;
+    const bool mirror = flip && flip[i];
     for (int oy = 0; oy < OH; ++oy) {
       const uint16_t* q = &ay.q[static_cast<size_t>(oy) * kResizeMaxTaps];
       const uint16_t* h0 = &h[static_cast<size_t>(ay.j0[oy] - ya) * row];
       for (size_t el = 0; el < row; ++el) {
         uint32_t s = 0;
         for (int k = 0; k < ay.n[oy]; ++k) s += q[k] * static_cast<uint32_t>(h0[k * row + el]);
-        o[oy * row + el] = static_cast<uint8_t>((s + (1u << 22)) >> 23);
+        // a mirrored output: column OW - 1 - ox, same channel
+        const size_t at = mirror ? row - 3 - 3 * (el / 3) + el % 3 : el;
+        o[oy * row + at] = static_cast<uint8_t>((s + (1u << 22)) >> 23);
       }
     }
   }

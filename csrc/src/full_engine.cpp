@@ -142,6 +142,9 @@ hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip:
   auto reduce = [&](int ksplit) {
     if (head && k_.bf16_head) {
       head->slabs = true;
+      if (head->views)  // N rows = N / views images
+        return hip::softmax_topk_views(ws_.get(), ksplit, static_cast<size_t>(N) * L.K, L.bias.get(), N / head->views,
+                                       head->views, L.K, head->k, head->idx, head->prob, nullptr, head->logits, s);
       float* lo = head->logits ? head->logits : L.K > hip::kSoftmaxTopkLdsRow ? out_f32 : nullptr;
       return hip::softmax_topk(ws_.get(), ksplit, static_cast<size_t>(N) * L.K, L.bias.get(), N, L.K, head->k, head->idx,
                                head->prob, lo, s);
@@ -193,6 +196,20 @@ hipError_t FullEngine::classify_u8(const uint8_t* x, int N, int k, int* idx, flo
   return run(nullptr, x, N, logits, s, mark, &h);
 }
 
+hipError_t FullEngine::classify_views(const float* x, int rows, int V, int k, int* idx, float* prob, float* logits,
+                                      hipStream_t s, bool mark) {
+  if (V < 1) return hipErrorInvalidValue;  // 0 would mean classify
+  const Head h{k, idx, prob, logits, false, V};
+  return run(x, nullptr, rows, logits, s, mark, &h);
+}
+
+hipError_t FullEngine::classify_views_u8(const uint8_t* x, int rows, int V, int k, int* idx, float* prob, float* logits,
+                                         hipStream_t s, bool mark) {
+  if (V < 1) return hipErrorInvalidValue;
+  const Head h{k, idx, prob, logits, false, V};
+  return run(nullptr, x, rows, logits, s, mark, &h);
+}
+
 void FullEngine::set_input_norm(const float* scale, const float* offset) {
   for (int c = 0; c < 3; ++c) norm_.sc[c] = scale[c], norm_.of[c] = offset[c];
 }
@@ -201,6 +218,11 @@ hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* log
                            const Head* head) {
   if (head && (head->k < 1 || head->k > cpu::kMaxTopK || head->k > classes_ || (N > 0 && (!head->idx || !head->prob))))
     return hipErrorInvalidValue;
+  // views: whole images per launch chunk
+  const int V = head ? head->views : 0;
+  if (V && (V > cpu::kMaxViews || N % V != 0 || chunk_ < V || classes_ > hip::kSoftmaxViewsMaxK))
+    return hipErrorInvalidValue;
+  const int step = V ? chunk_ / V * V : chunk_;
   head_ = nullptr;
   if (mark && !mark_) ANX_TRY(mark_.try_create(hipEventDisableTiming));
   using hip::OutViewB;
@@ -218,8 +240,8 @@ hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* log
       return hipErrorStreamCaptureUnsupported;
     ANX_TRY(xdec_.try_alloc(static_cast<size_t>(chunk_) * kImage));
   }
-  for (int n0 = 0; n0 < N; n0 += chunk_) {
-    const int n = std::min(chunk_, N - n0);
+  for (int n0 = 0; n0 < N; n0 += step) {
+    const int n = std::min(step, N - n0);
     const float* xn = xf ? xf + static_cast<size_t>(n0) * kImage : xdec_.get();
     if (xu && !u8_ring) ANX_TRY(hip::decode_u8(xu + static_cast<size_t>(n0) * kImage, xdec_.get(), n * kImage, norm_, s));
     input_ = !xu ? "f32" : u8_ring ? "u8_ring" : "u8_decode";
@@ -275,11 +297,14 @@ hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* log
       continue;
     }
     // classify: this chunk's outputs; logits the caller does not take go to the workspace
-    Head h{head->k, head->idx + static_cast<size_t>(n0) * head->k, head->prob + static_cast<size_t>(n0) * head->k,
-           logits ? logits + static_cast<size_t>(n0) * classes_ : nullptr, false};
+    const size_t o0 = static_cast<size_t>(V ? n0 / V : n0) * head->k;  // outputs: one row per image
+    Head h{head->k, head->idx + o0, head->prob + o0, logits ? logits + static_cast<size_t>(n0) * classes_ : nullptr,
+           false, V};
     float* const z = h.logits ? h.logits : hlog_.get();
     ANX_TRY(conv(L_[7], n, 1, 1, f8_, OutViewB{nullptr, 1, 1, classes_, 0, 0, 0}, z, false, s, &h));
-    if (!h.slabs)  // on the written logits (a row too long for the head's LDS is read back from them)
+    if (!h.slabs && V)
+      ANX_TRY(hip::softmax_topk_views(z, 1, 0, nullptr, n / V, V, classes_, h.k, h.idx, h.prob, nullptr, nullptr, s));
+    else if (!h.slabs)  // on the written logits (a row too long for the head's LDS is read back from them)
       ANX_TRY(hip::softmax_topk(z, 1, 0, nullptr, n, classes_, h.k, h.idx, h.prob,
                                 classes_ > hip::kSoftmaxTopkLdsRow ? z : nullptr, s));
     head_ = h.slabs ? "slabs" : "logits";

@@ -12,6 +12,8 @@
 // (about 290 rows for 16 output rows at 16x), which is why rows are streamed and the R x NI vertical accumulators
 // live in registers: LDS holds only G source rows, whatever the scale. The band's output (R x 3 OW contiguous
 // bytes, from any byte address) is assembled in the staging area and leaves as 16-B stores with a byte head / tail.
+// A launch may carry one flag byte per output: a flagged output is mirrored (columns reversed), which only changes
+// where its bytes land in that assembly; several outputs may name one source image (the ten views of an image).
 //
 // The reference has no resampling stage: its programs fill float arrays (v1_serial/src/main.cpp:18-43).
 #include <hip/hip_runtime.h>
@@ -59,10 +61,13 @@ __device__ __forceinline__ void copy_bytes(uint8_t* dst, const uint8_t* src, uns
 // (a padded tap reads at most 9 bytes past its staged row, inside this workgroup's LDS, times zero); KT = 0: the
 // weights stay in LDS and the pass loops over each element's own tap count.
 // G source rows of LP bytes are staged per step; TS: entries per horizontal tap row; stage: bytes of the staging area.
-template <int NI, int R, int KT>
+// Flip: empty, or one `const uint8_t*`, the launch's flag bytes (flip[img] != 0: a mirrored output). With the pack
+// empty the kernel has no such parameter and no code for it.
+template <int NI, int R, int KT, class... Flip>
 __global__ void __launch_bounds__(kThreads) resize_crop_u8_kernel(const ImageDesc* __restrict__ descs,
                                                                   uint8_t* __restrict__ out, int OH, int OW, int bands,
-                                                                  int G, int LP, int TS, unsigned stage) {
+                                                                  int G, int LP, int TS, unsigned stage, Flip... flip) {
+  static_assert(sizeof...(Flip) <= 1, "at most one flag array");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   uint16_t* vq = reinterpret_cast<uint16_t*>(lds + stage);
   int* vj0 = reinterpret_cast<int*>(vq + R * kResizeMaxTaps);
@@ -171,17 +176,34 @@ __global__ void __launch_bounds__(kThreads) resize_crop_u8_kernel(const ImageDes
     __syncthreads();  // the staged rows are free again (and, after the last step, the staging area is)
   }
 
-  // the band's bytes, assembled at their global address mod 16, then stored wide
+  // the band's bytes, assembled at their global address mod 16, then stored wide. A mirrored output (the flag is
+  // uniform over the workgroup) differs only here: element (ox, c) lands at column OW - 1 - ox.
   uint8_t* op = out + (static_cast<size_t>(img) * OH + oy0) * OW3;
   const unsigned o0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>(op) & 15u);
   uint8_t* so = lds + o0;
+  if constexpr (sizeof...(Flip) == 0) {
 #pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int e = t + i * kThreads;
-    if (e < OW3) {
+    for (int i = 0; i < NI; ++i) {
+      const int e = t + i * kThreads;
+      if (e < OW3) {
 #pragma unroll
-      for (int r = 0; r < R; ++r)
-        if (r < rows) so[r * OW3 + e] = static_cast<uint8_t>((acc[i][r] + (1u << 22)) >> 23);
+        for (int r = 0; r < R; ++r)
+          if (r < rows) so[r * OW3 + e] = static_cast<uint8_t>((acc[i][r] + (1u << 22)) >> 23);
+      }
+    }
+  } else {
+    const uint8_t* const flags = (flip, ...);
+    const bool mirror = flags[img] != 0;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int e = t + i * kThreads;
+      if (e < OW3) {
+        const int ox = e / 3;
+        const int at = mirror ? 3 * (OW - 1 - ox) + (e - 3 * ox) : e;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if (r < rows) so[r * OW3 + at] = static_cast<uint8_t>((acc[i][r] + (1u << 22)) >> 23);
+      }
     }
   }
   __syncthreads();
@@ -192,7 +214,13 @@ __global__ void __launch_bounds__(kThreads) resize_crop_u8_kernel(const ImageDes
 
 hipError_t resize_crop_u8(const ImageDesc* dev, const ImageDesc* host, int n, uint8_t* out, int OH, int OW,
                           hipStream_t s) {
+  return resize_crop_u8(dev, host, nullptr, nullptr, n, out, OH, OW, s);
+}
+
+hipError_t resize_crop_u8(const ImageDesc* dev, const ImageDesc* host, const uint8_t* flip_dev, const uint8_t* flip_host,
+                          int n, uint8_t* out, int OH, int OW, hipStream_t s) {
   if (resize_crop_check(host, n, OH, OW)) return hipErrorInvalidValue;
+  if ((flip_dev == nullptr) != (flip_host == nullptr)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (!dev || !out) return hipErrorInvalidValue;
   const int OW3 = 3 * OW;
@@ -220,15 +248,21 @@ hipError_t resize_crop_u8(const ImageDesc* dev, const ImageDesc* host, int n, ui
   const long long grid = static_cast<long long>(bands) * n;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
   const dim3 g(static_cast<unsigned>(grid));
-#define ANX_RC_LAUNCH(NI_, R_)                                                                                  \
-  do {                                                                                                          \
-    if (TS <= kRegTaps)                                                                                         \
-      resize_crop_u8_kernel<NI_, R_, kRegTaps><<<g, kThreads, lds, s>>>(dev, out, OH, OW, bands,                \
-                                                                         static_cast<int>(G),                    \
-                                                                         static_cast<int>(LP), TS, stage);       \
-    else                                                                                                        \
-      resize_crop_u8_kernel<NI_, R_, 0><<<g, kThreads, lds, s>>>(dev, out, OH, OW, bands, static_cast<int>(G),  \
-                                                                  static_cast<int>(LP), TS, stage);              \
+#define ANX_RC_KERNEL(NI_, R_, KT_)                                                                              \
+  do {                                                                                                           \
+    if (flip_dev)                                                                                                \
+      resize_crop_u8_kernel<NI_, R_, KT_, const uint8_t*><<<g, kThreads, lds, s>>>(                              \
+          dev, out, OH, OW, bands, static_cast<int>(G), static_cast<int>(LP), TS, stage, flip_dev);              \
+    else                                                                                                         \
+      resize_crop_u8_kernel<NI_, R_, KT_><<<g, kThreads, lds, s>>>(dev, out, OH, OW, bands, static_cast<int>(G), \
+                                                                    static_cast<int>(LP), TS, stage);            \
+  } while (0)
+#define ANX_RC_LAUNCH(NI_, R_)          \
+  do {                                  \
+    if (TS <= kRegTaps)                 \
+      ANX_RC_KERNEL(NI_, R_, kRegTaps); \
+    else                                \
+      ANX_RC_KERNEL(NI_, R_, 0);        \
   } while (0)
   if (ni <= 1)
     ANX_RC_LAUNCH(1, 16);
@@ -239,6 +273,7 @@ hipError_t resize_crop_u8(const ImageDesc* dev, const ImageDesc* host, int n, ui
   else
     ANX_RC_LAUNCH(6, 8);
 #undef ANX_RC_LAUNCH
+#undef ANX_RC_KERNEL
   return hipGetLastError();
 }
 

@@ -23,16 +23,12 @@
 #include <cstdint>
 
 #include "anx/ops.hpp"
+#include "softmax_head.hpp"
 
 namespace anx::hip {
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-constexpr unsigned kThreads = 256, kWaves = kThreads / 64;
-
-__device__ inline float rank_key(float v) { return v != v ? -INFINITY : v; }
-// (va, ia) ranks before (vb, ib)
-__device__ inline bool ranks_before(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
+using namespace head;  // the workgroup shape, f32x4, rank_key, ranks_before, aligned16: shared with the view head
 
 template <bool VEC, bool STAGED>
 __global__ void __launch_bounds__(kThreads) softmax_topk_kernel(const float* src, int ksplit, size_t slab_stride,
@@ -130,8 +126,6 @@ __global__ void __launch_bounds__(kThreads) softmax_topk_kernel(const float* src
     }
   }
 }
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace
 

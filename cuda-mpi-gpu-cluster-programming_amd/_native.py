@@ -87,6 +87,10 @@ _SIGS = {
     "anx_cpu_softmax_topk": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _P, _P, _P]),
     "anx_resize_crop_u8": (_I, [_P, _P, _I, _P, _I, _I, _P]),
     "anx_cpu_resize_crop_u8": (_I, [_P, _I, _P, _I, _I]),
+    "anx_resize_crop_u8_flip": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _P]),
+    "anx_cpu_resize_crop_u8_flip": (_I, [_P, _P, _I, _P, _I, _I]),
+    "anx_softmax_topk_views": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "anx_cpu_softmax_topk_views": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "anx_cpu_engine_set_input_norm": (_I, [_P, _P, _P]),
     "anx_cpu_engine_forward_u8": (_I, [_P, _P, _I, _P]),
     "anx_cpu_engine_tile_forward_u8": (_I, [_P, _P, _I, C.POINTER(TileC), _P]),
@@ -181,6 +185,8 @@ _BF16_SIGS = {
     "anx_full_classify": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I]),
     "anx_full_classify_u8": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I]),
     "anx_full_last_head": (_I, [_P, C.c_char_p, _SZ]),
+    "anx_full_classify_views": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I]),
+    "anx_full_classify_views_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I]),
 }
 _bf16 = None
 

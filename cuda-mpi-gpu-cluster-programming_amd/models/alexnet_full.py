@@ -17,7 +17,9 @@ graph) and the float kernels run on it.
 
 Byte images of any other size go through :meth:`AlexNetFull.forward_images` / :meth:`AlexNetFull.classify_images`:
 one :func:`anx.ops.resize_crop_u8` launch (antialiased resize + centre crop, integer arithmetic) into a byte workspace
-of the model, then the byte path above.
+of the model, then the byte path above. ``classify_images(views="ten")`` is AlexNet's ten-view protocol (corner and
+centre crops and their mirror images, one resize launch for all of them) on ``classify(views=10)``, whose head
+kernel averages the views' softmax outputs on chip (:func:`anx.ops.softmax_topk_views`).
 """
 from __future__ import annotations
 
@@ -212,35 +214,57 @@ class AlexNetFull:
             else:
                 fn = "anx_full_forward_u8" if u8 else "anx_full_forward"
             nat.call(fn, self._h, x.data_ptr(), x.shape[0], z.data_ptr(), stream)
-        else:
+        elif len(head) == 3:
             k, idx, prob = head
             nat.call("anx_full_classify_u8" if u8 else "anx_full_classify", self._h, x.data_ptr(), x.shape[0], k,
                      idx.data_ptr(), prob.data_ptr(), z.data_ptr() if z is not None else None, stream, int(mark))
+        else:  # views: x holds V rows per row of idx / prob
+            k, idx, prob, V = head
+            nat.call("anx_full_classify_views_u8" if u8 else "anx_full_classify_views", self._h, x.data_ptr(),
+                     x.shape[0], V, k, idx.data_ptr(), prob.data_ptr(), z.data_ptr() if z is not None else None, stream,
+                     int(mark))
 
     def _run(self, x, z, head, free: bool = False, pre_lane=None, on_lane=None) -> None:
         """:meth:`_launch` of every lane's slice through :mod:`anx.models.lanes`: forked and joined within the
-        call, or (``free``) left running on the lanes' streams until :meth:`join`."""
+        call, or (``free``) left running on the lanes' streams until :meth:`join`. A head with views
+        ``(k, indices, probs, V)`` splits on image boundaries: the lanes divide the ``N`` images, and image ``i`` is
+        rows ``i V .. (i + 1) V`` of ``x`` and ``z``."""
+        views = tuple(head[3:]) if head is not None else ()
+        V = views[0] if views else 1
+
         def run(i, lo, hi, st=None, lead=False):
             eng = self._lane(i)
-            eng._ensure(hi - lo)
-            eng._launch(x[lo:hi], z[lo:hi] if z is not None else None,
-                        (head[0], head[1][lo:hi], head[2][lo:hi]) if head is not None else None,
+            eng._ensure((hi - lo) * V)
+            eng._launch(x[lo * V:hi * V], z[lo * V:hi * V] if z is not None else None,
+                        (head[0], head[1][lo:hi], head[2][lo:hi], *views) if head is not None else None,
                         st.cuda_stream if st is not None else None, lead)
             if lead:
                 return lambda s: nat.call("anx_full_wait_mark", eng._h, s.cuda_stream)
 
         if free:
             # growing an engine may synchronise the device: before its lane's waits, not between them and the call
-            self._streams.run_free(x.shape[0], run, pre_lane, on_lane,
-                                   prepare=lambda i, lo, hi: self._lane(i)._ensure(hi - lo))
+            self._streams.run_free(x.shape[0] // V, run, pre_lane, on_lane,
+                                   prepare=lambda i, lo, hi: self._lane(i)._ensure((hi - lo) * V))
         else:
-            self._streams.run_joined(x.shape[0], run)
+            self._streams.run_joined(x.shape[0] // V, run)
 
-    def _check_head(self, x, k, idx, prob):
+    def _check_views(self, x, views) -> int | None:
+        """``views`` of :meth:`classify`: None, or the rows per image of ``x``."""
+        if views is None:
+            return None
+        if not isinstance(views, int) or isinstance(views, bool) or not 1 <= views <= 32:
+            raise ValueError(f"views must be None or an integer 1 .. 32, got {views!r}")
+        if x.shape[0] % views:
+            raise ValueError(f"{x.shape[0]} rows are no whole number of images of {views} views")
+        if self.classes > 7680:
+            raise ValueError("the view-averaging head takes at most 7680 classes")
+        return views
+
+    def _check_head(self, x, k, idx, prob, views=None):
         """classify's outputs: validated like ``out`` in :meth:`_check`, allocated when not given."""
         if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= min(self.classes, 16):
             raise ValueError(f"k must be an integer with 1 <= k <= min(classes, 16) = {min(self.classes, 16)}, got {k!r}")
-        shape = (x.shape[0], k)
+        shape = (x.shape[0] // (views or 1), k)
         outs = []
         for t, dt, name in ((idx, torch.int32, "indices"), (prob, torch.float32, "probabilities")):
             if t is None:
@@ -251,36 +275,60 @@ class AlexNetFull:
             outs.append(t)
         return outs
 
-    def classify(self, x: torch.Tensor, k: int = 5, *, return_logits: bool = False, out=None):
+    def classify(self, x: torch.Tensor, k: int = 5, *, views: int | None = None, return_logits: bool = False, out=None):
         """x as in :meth:`forward` -> ``(indices [N,k] int32, probs [N,k] fp32)``: the ``k`` most likely classes of
         each image (logit descending, then class index ascending) and their softmax probabilities, equal bit for bit
         to ``anx.ops.softmax_topk(forward(x), k)``. ``return_logits`` appends the ``[N, classes]`` logits, the bits
         :meth:`forward` gives. ``out``: ``(indices, probs)`` or ``(indices, probs, logits)`` tensors to write into.
         Where FC8 ran split-K, the head kernel reduces the slabs itself (knob ``bf16_head``), so without
-        ``return_logits`` the logits never reach device memory; :meth:`last_head` tells. Lanes as :meth:`forward`."""
+        ``return_logits`` the logits never reach device memory; :meth:`last_head` tells. Lanes as :meth:`forward`.
+
+        ``views=V`` (1 to 32): ``x`` is ``[N * V,227,227,3]``, ``V`` consecutive views per image, and the outputs are
+        ``[N,k]``: the ``k`` classes of the largest mean softmax probability over an image's views and that mean,
+        equal bit for bit to ``anx.ops.softmax_topk_views(forward(x), V, k)``; the head kernel averages on chip, on
+        FC8's slabs where there are any. Lanes split on image boundaries; ``return_logits`` gives
+        ``[N * V, classes]``. ``views=None`` is the call without views."""
         out = tuple(out) if out is not None else ()
         if len(out) not in (0, 2, 3):
             raise ValueError("out must be (indices, probs) or (indices, probs, logits)")
         want_logits = return_logits or len(out) == 3
         self._check_x(x)
+        views = self._check_views(x, views)
         z = self._check(x, out[2] if len(out) == 3 else None) if want_logits else None
-        idx, prob = self._check_head(x, k, *(out[:2] if out else (None, None)))
-        self._run(x, z, (k, idx, prob))
+        idx, prob = self._check_head(x, k, *(out[:2] if out else (None, None)), views)
+        self._run(x, z, (k, idx, prob) if views is None else (k, idx, prob, views))
         return (idx, prob, z) if want_logits else (idx, prob)
 
-    def _preprocess(self, images, resize) -> torch.Tensor:
+    def _preprocess(self, images, resize, views=None) -> torch.Tensor:
         """``images`` (as :func:`anx.ops.resize_crop_u8` takes them) -> ``uint8 [N,227,227,3]`` in the model-owned
-        byte workspace, by one :func:`anx.ops.resize_crop_u8` launch on the current stream (``center_box`` boxes)."""
-        from ..ops import resize_crop_u8
+        byte workspace, by one :func:`anx.ops.resize_crop_u8` launch on the current stream (``center_box`` boxes).
+        ``views="ten"``: ``[10 N,227,227,3]``, each image's :func:`anx.ops.ten_crop_boxes` views, still one launch
+        (every view names its source image, none is copied)."""
+        from ..ops import resize_crop_u8, ten_crop_boxes
+        if views not in (None, "ten"):
+            raise ValueError(f'views must be None or "ten", got {views!r}')
         n = images.shape[0] if isinstance(images, torch.Tensor) else len(images)
         for im in ((images,) if isinstance(images, torch.Tensor) else images):
             if isinstance(im, torch.Tensor) and im.device != self.device:
                 raise ValueError(f"expected images on {self.device}, got one on {im.device}")
+        more = {}
+        if views == "ten":
+            boxes, flips, source = [], [], []
+            for i in range(n):
+                im = images[i]
+                if not isinstance(im, torch.Tensor) or im.dim() != 3:
+                    raise ValueError("every image must be a uint8 [H,W,3] tensor")
+                b, f = ten_crop_boxes(im.shape[0], im.shape[1], resize, 227)
+                boxes += b
+                flips += f
+                source += [i] * 10
+            more = {"boxes": boxes, "flips": flips, "source": source}
+            n *= 10
         if self._img_ws is None or n > self._img_cap:
             # the old workspace goes back to torch's allocator, which hands it out again in stream order
             self._img_cap = max(1, n)
             self._img_ws = torch.empty((self._img_cap, 227, 227, 3), device=self.device, dtype=torch.uint8)
-        return resize_crop_u8(images, 227, resize, out=self._img_ws[:n])
+        return resize_crop_u8(images, 227, resize, out=self._img_ws[:n], **more)
 
     def forward_images(self, images, out: torch.Tensor | None = None, resize: int | None = 256) -> torch.Tensor:
         """Byte images of any size -> logits ``[N, classes]``: ``images`` is a list of ``uint8 [H,W,3]`` tensors (each
@@ -294,19 +342,29 @@ class AlexNetFull:
         the largest batch before capturing a graph, as for the ``"u8_decode"`` workspace."""
         return self.forward(self._preprocess(images, resize), out)
 
-    def classify_images(self, images, k: int = 5, resize: int | None = 256, return_logits: bool = False):
+    def classify_images(self, images, k: int = 5, resize: int | None = 256, return_logits: bool = False, views=None):
         """:meth:`classify` of byte images of any size (``images``, ``resize`` and the workspace as in
-        :meth:`forward_images`): equal bit for bit to ``classify(anx.ops.resize_crop_u8(images, 227, resize), k)``."""
-        return self.classify(self._preprocess(images, resize), k, return_logits=return_logits)
+        :meth:`forward_images`): equal bit for bit to ``classify(anx.ops.resize_crop_u8(images, 227, resize), k)``.
+
+        ``views="ten"``: AlexNet's ten-view protocol. Each image's four corner crops, centre crop and their mirror
+        images (:func:`anx.ops.ten_crop_boxes`, all at the centre crop's scale) are cut by one
+        :func:`anx.ops.resize_crop_u8` launch of ``10 N`` outputs into the byte workspace, and
+        ``classify(..., views=10)`` ranks the mean of the ten softmax outputs; ``return_logits`` gives
+        ``[10 N, classes]``."""
+        return self.classify(self._preprocess(images, resize, views), k, views=10 if views == "ten" else None,
+                             return_logits=return_logits)
 
     def classify_async(self, x: torch.Tensor, idx_out: torch.Tensor, prob_out: torch.Tensor, k: int = 5, on_lane=None,
-                       pre_lane=None):
+                       pre_lane=None, views: int | None = None):
         """:meth:`classify` in the throughput form of :meth:`forward_async` (same contract: free-running lanes on
         their own streams, lane i starting at lane i-1's mid-forward mark when all are idle, never joined per call):
-        writes ``idx_out`` ``[N,k]`` int32 and ``prob_out`` ``[N,k]`` fp32. :meth:`join` before reading them."""
+        writes ``idx_out`` ``[N,k]`` int32 and ``prob_out`` ``[N,k]`` fp32. :meth:`join` before reading them.
+        ``views`` as in :meth:`classify` (the hooks then get image bounds, not row bounds)."""
         self._check_x(x)
-        idx_out, prob_out = self._check_head(x, k, idx_out, prob_out)
-        self._run(x, None, (k, idx_out, prob_out), True, pre_lane, on_lane)
+        views = self._check_views(x, views)
+        idx_out, prob_out = self._check_head(x, k, idx_out, prob_out, views)
+        self._run(x, None, (k, idx_out, prob_out) if views is None else (k, idx_out, prob_out, views), True, pre_lane,
+                  on_lane)
         return idx_out, prob_out
 
     def last_head(self, lane: int = 0) -> str | None:

@@ -34,7 +34,7 @@ from .. import _native as nat
 from ..config import conv_out_dim, pool_out_dim
 
 __all__ = ["conv2d", "relu", "maxpool", "lrn", "maxpool_lrn", "decode_u8", "softmax_topk", "resize_crop_u8",
-           "center_box", "clear_cache"]
+           "center_box", "ten_crop_boxes", "softmax_topk_views", "clear_cache"]
 
 _LRN_MODES = {"div_n": 0, "raw": 1}
 _pack_cache: dict = {}
@@ -234,9 +234,49 @@ def _image_descs(geo, OH: int, OW: int, resize, boxes):
     return desc
 
 
-def resize_crop_u8(images, size=227, resize: int | None = 256, boxes=None, out: torch.Tensor | None = None) -> torch.Tensor:
+def ten_crop_boxes(H: int, W: int, resize: int | None = 256, size=227):
+    """The ten views of an ``H x W`` image that AlexNet's evaluation protocol takes, as ``(boxes, flips)`` for
+    :func:`resize_crop_u8`, ten of each: the four corner crops and the centre crop, then the same five mirrored.
+    All ten share the scale of ``center_box(H, W, resize, size)`` (its ``bh x bw``); the origins in half pixels are
+    ``(0, 0)``, ``(0, 2 (W - bw))``, ``(2 (H - bh), 0)``, ``(2 (H - bh), 2 (W - bw))`` and the centre
+    ``(H - bh, W - bw)``. ``resize=None`` makes the box the whole image, so the five origins coincide."""
+    _, _, bh, bw = center_box(H, W, resize, size)
+    y1, x1 = 2 * (int(H) - bh), 2 * (int(W) - bw)
+    five = [(0, 0, bh, bw), (0, x1, bh, bw), (y1, 0, bh, bw), (y1, x1, bh, bw), (y1 // 2, x1 // 2, bh, bw)]
+    return five + five, [False] * 5 + [True] * 5
+
+
+def _flip_flags(flips, n: int) -> np.ndarray:
+    """``flips`` of :func:`resize_crop_u8` as ``n`` flag bytes; anything but ``n`` booleans raises."""
+    if isinstance(flips, torch.Tensor):
+        if flips.dtype != torch.bool or flips.dim() != 1:
+            raise ValueError("resize_crop_u8: flips must be booleans, one per output")
+        flips = flips.cpu().numpy()
+    elif isinstance(flips, np.ndarray):
+        if flips.dtype != np.bool_ or flips.ndim != 1:
+            raise ValueError("resize_crop_u8: flips must be booleans, one per output")
+    else:
+        try:
+            flips = list(flips)
+        except TypeError as e:
+            raise ValueError("resize_crop_u8: flips must be booleans, one per output") from e
+        if not all(isinstance(f, (bool, np.bool_)) for f in flips):
+            raise ValueError("resize_crop_u8: flips must be booleans, one per output")
+        flips = np.array(flips, dtype=np.bool_)
+    if flips.shape[0] != n:
+        raise ValueError(f"resize_crop_u8: one flip per output: {flips.shape[0]} for {n} outputs")
+    return np.ascontiguousarray(flips).astype(np.uint8)
+
+
+def resize_crop_u8(images, size=227, resize: int | None = 256, boxes=None, out: torch.Tensor | None = None,
+                   flips=None, source=None) -> torch.Tensor:
     """Byte images of any size -> ``uint8 [N, OH, OW, 3]``: each image's box resampled onto the output with torch /
     PIL's antialiased bilinear (triangle) filter, in fixed point, one native kernel for the whole batch.
+
+    ``flips``: one boolean per output; a flipped output is the unflipped one with its columns reversed,
+    ``out[oy][OW-1-ox][c]`` (default: none, today's call). ``source``: ``source[i]`` is the index of the image that
+    output ``i`` is cut from (default: output ``i`` from image ``i``); ``boxes`` and ``flips`` are then per output and
+    the result has ``len(source)`` outputs, so several views share one source image without repeating tensors.
 
     ``images``: a list of ``uint8 [H,W,3]`` tensors (each its own size) or one ``[N,H,W,3]`` tensor, all on one
     device; the last two dims contiguous, the row stride free (a column slice of a bigger image is fine).
@@ -255,10 +295,22 @@ def resize_crop_u8(images, size=227, resize: int | None = 256, boxes=None, out: 
     if not (1 <= OH <= RESIZE_MAX_OUT and 1 <= OW <= RESIZE_MAX_OUT):
         raise ValueError(f"resize_crop_u8: output size must be 1 .. {RESIZE_MAX_OUT}, got {(OH, OW)}")
     geo, dev = _image_geometry(images)
+    if source is not None:
+        try:
+            src = np.asarray(source.cpu() if isinstance(source, torch.Tensor) else source)
+        except (TypeError, ValueError) as e:
+            raise ValueError("resize_crop_u8: source must be image indices, one per output") from e
+        if src.ndim != 1 or (src.size and src.dtype.kind not in "iu"):
+            raise ValueError("resize_crop_u8: source must be image indices, one per output")
+        src = src.astype(np.int64)
+        if src.size and not (src.min() >= 0 and src.max() < geo.shape[0]):
+            raise ValueError(f"resize_crop_u8: source indices must be 0 .. {geo.shape[0] - 1}")
+        geo = geo[src]
     n = geo.shape[0]
     if dev is None:
         dev = out.device if out is not None else torch.device("cpu")
     desc = _image_descs(geo, OH, OW, resize, boxes)
+    flags = _flip_flags(flips, n) if flips is not None else None
     shape = (n, OH, OW, 3)
     if out is None:
         out = torch.empty(shape, device=dev, dtype=torch.uint8)
@@ -268,13 +320,21 @@ def resize_crop_u8(images, size=227, resize: int | None = 256, boxes=None, out: 
     if n == 0:
         return out
     host = torch.from_numpy(desc.view(np.uint8))
+    fhost = torch.from_numpy(flags) if flags is not None else None
     if dev.type == "cuda":
         with torch.cuda.device(dev):
             ddev = host.to(dev, non_blocking=True)  # on the current stream, ahead of the kernel
-            nat.call("anx_resize_crop_u8", ddev.data_ptr(), host.data_ptr(), n, out.data_ptr(), OH, OW,
-                     nat.stream_ptr(dev))
-    else:
+            if fhost is None:
+                nat.call("anx_resize_crop_u8", ddev.data_ptr(), host.data_ptr(), n, out.data_ptr(), OH, OW,
+                         nat.stream_ptr(dev))
+            else:
+                fdev = fhost.to(dev, non_blocking=True)
+                nat.call("anx_resize_crop_u8_flip", ddev.data_ptr(), host.data_ptr(), fdev.data_ptr(),
+                         fhost.data_ptr(), n, out.data_ptr(), OH, OW, nat.stream_ptr(dev))
+    elif fhost is None:
         nat.call("anx_cpu_resize_crop_u8", host.data_ptr(), n, out.data_ptr(), OH, OW)
+    else:
+        nat.call("anx_cpu_resize_crop_u8_flip", host.data_ptr(), fhost.data_ptr(), n, out.data_ptr(), OH, OW)
     return out
 
 
@@ -327,6 +387,66 @@ def softmax_topk(logits: torch.Tensor | None = None, k: int = 5, *, slabs: torch
         else:
             nat.call("anx_cpu_softmax_topk", *args)
     return (idx, prob, z) if return_logits else (idx, prob)
+
+
+MAX_VIEWS = 32           # kMaxViews (anx/ops.hpp)
+_VIEWS_MAX_K = 7680      # kSoftmaxViewsMaxK: two rows of the view-averaging head in LDS on the GPU
+
+
+def softmax_topk_views(logits: torch.Tensor | None = None, views: int | None = None, k: int = 5, *,
+                       slabs: torch.Tensor | None = None, bias: torch.Tensor | None = None, return_probs: bool = False):
+    """The view-averaging head: the rows are ``views`` consecutive views per image, ``[N * views, K]`` image-major
+    (row ``i * views + v`` is view ``v`` of image ``i``), given as ``logits`` or as ``slabs`` ``[ksplit, N * views, K]``
+    (+ ``bias``) exactly as :func:`softmax_topk` takes them. Per row ``p_v = exp(z - max) / sum(exp(z - max))`` in
+    fp32 (:func:`softmax_topk`'s expressions); per image ``pbar = ((p_0 + p_1) + ... + p_{V-1}) / float(V)`` in fp32,
+    adding in view order. Returns ``(indices int32 [N,k], probs float32 [N,k])``: the ``k`` classes of the largest
+    ``pbar`` (descending, then index ascending) and ``pbar`` there; with ``return_probs`` also the whole ``[N,K]``
+    ``pbar``. One native kernel; ``1 <= views <= 32``, ``1 <= k <= min(K, 16)``, and ``K <= 7680`` on the GPU.
+
+    The ranking is by probability, not by logit. With ``views=1`` the probabilities are :func:`softmax_topk`'s bits,
+    but classes whose probabilities underflow to the same value (zero, say) tie here and go to the lower index, where
+    :func:`softmax_topk` still orders them by their logits. The host function ``cpu::softmax_topk_views`` (CPU
+    tensors) is the definition; ``expf`` differs between host and device, so both are held to an fp64 softmax mean
+    rather than to each other's bits."""
+    if (logits is None) == (slabs is None):
+        raise ValueError("softmax_topk_views: give logits [N*V,K] or slabs [ksplit,N*V,K], not both")
+    if not isinstance(views, int) or isinstance(views, bool) or not 1 <= views <= MAX_VIEWS:
+        raise ValueError(f"softmax_topk_views: views must be an integer 1 .. {MAX_VIEWS}, got {views!r}")
+    src = logits if slabs is None else slabs
+    _check(src, "softmax_topk_views")
+    if slabs is None:
+        if src.dim() != 2:
+            raise ValueError("softmax_topk_views: logits must be [N*V,K]")
+        if bias is not None:
+            raise ValueError("softmax_topk_views: a bias goes with slabs")
+        ksplit, (M, K) = 1, src.shape
+    else:
+        if src.dim() != 3 or src.shape[0] < 1:
+            raise ValueError("softmax_topk_views: slabs must be [ksplit,N*V,K] with ksplit >= 1")
+        ksplit, M, K = src.shape
+    if M % views:
+        raise ValueError(f"softmax_topk_views: {M} rows are no whole number of images of {views} views")
+    if K < 1 or not 1 <= int(k) <= min(K, MAX_TOPK):
+        raise ValueError(f"softmax_topk_views: need 1 <= k <= min(K, {MAX_TOPK}), got k = {k} for K = {K}")
+    if src.is_cuda and K > _VIEWS_MAX_K:
+        raise ValueError(f"softmax_topk_views: at most {_VIEWS_MAX_K} classes on the GPU, got {K}")
+    if bias is not None:
+        _check(bias, "softmax_topk_views bias")
+        if tuple(bias.shape) != (K,) or bias.device != src.device:
+            raise ValueError("softmax_topk_views: bias must be [K] on the source's device")
+    k, N = int(k), M // views
+    idx = torch.empty((N, k), device=src.device, dtype=torch.int32)
+    prob = torch.empty((N, k), device=src.device, dtype=torch.float32)
+    probs = torch.empty((N, K), device=src.device, dtype=torch.float32) if return_probs else None
+    if N:
+        args = (src.data_ptr(), ksplit, M * K, bias.data_ptr() if bias is not None else None, N, views, K, k,
+                idx.data_ptr(), prob.data_ptr(), probs.data_ptr() if probs is not None else None, None)
+        if src.is_cuda:
+            with torch.cuda.device(src.device):
+                nat.call("anx_softmax_topk_views", *args, nat.stream_ptr(src.device))
+        else:
+            nat.call("anx_cpu_softmax_topk_views", *args)
+    return (idx, prob, probs) if return_probs else (idx, prob)
 
 
 def relu(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
