@@ -141,56 +141,60 @@ struct FullPathRecord {
   } gemm[7];
 };
 
+// One call of the full model, as a value: what goes in, what comes out, and which head runs on the logits.
+//  * Input: x is [rows,227,227,3] on the device, fp32, or bytes (u8) from any byte address. A byte b of channel c
+//    means fmaf(float(b), scale[c], offset[c]) (cpu::decode_u8; set_input_norm, default 1/255, 0), and the logits and
+//    every tap equal those of the float call fed the decoded image, bit for bit. With the row-band Conv1 on the image
+//    (bf16_conv1 2) and Knobs::bf16_u8 that kernel loads the bytes ("u8_ring": no float copy of the input exists);
+//    everywhere else hip::decode_u8 writes the launch chunk as fp32 into a workspace and the float path runs
+//    unchanged ("u8_decode"). The first byte call that needs the workspace allocates it (chunk-sized, freed with the
+//    engine), never inside a stream capture: warm up once before capturing a graph. No other call allocates.
+//  * k == 0, the plain forward: logits [rows,classes] fp32 device.
+//  * k > 0, the classifier head: idx int32 [N][k] and prob fp32 [N][k] device, the k most likely classes of each image
+//    and their probabilities; logits (nullable) as above, the bits the plain forward writes (logits nobody asked for
+//    go to a workspace of the engine). Launch chunks advance the outputs by n * k. Where FC8 went through split-K
+//    slabs the head kernel reduces them itself with FC8's bias in place of splitk_reduce_bf16 (Knobs::bf16_head; 0:
+//    the reduce writes the logits and the head runs on those); where FC8 writes fp32 directly the head runs on the
+//    logits. last_head() tells.
+//  * views == 0: N = rows, ranked by logit (cpu::softmax_topk is the definition). views = V in 1 .. kMaxViews: x holds
+//    rows = N * V images, image-major (row i * V + v is view v of image i), and idx / prob rank the mean of each
+//    image's V softmax rows (cpu::softmax_topk_views; by probability, so V = 1 is not views == 0). A launch chunk then
+//    holds whole images: the chunk step is the largest multiple of V the engine's chunk holds.
+//  * mark: record the engine's mark event on the stream once Conv2 + Pool2/LRN of the first chunk are enqueued (about
+//    half of the forward), for wait_mark.
+struct FullCall {
+  const void* x = nullptr;
+  bool u8 = false;
+  int rows = 0;
+  float* logits = nullptr;
+  bool mark = false;
+  int k = 0;
+  int* idx = nullptr;
+  float* prob = nullptr;
+  int views = 0;
+};
+
 class FullEngine {
  public:
   FullEngine(const FullWeights& w, int classes, int max_batch, int groups2 = 1, LrnMode lrn = LrnMode::DivN,
              const Knobs& k = default_knobs());
   FullEngine(const FullEngine&) = delete;
   FullEngine& operator=(const FullEngine&) = delete;
-  // x: [N,227,227,3] fp32 device; logits: [N,classes] fp32 device.
-  hipError_t forward(const float* x, int N, float* logits, hipStream_t s, bool mark = false);
-  // Byte input: x [N,227,227,3] uint8 device, from any byte address. A byte b of channel c means
-  // fmaf(float(b), scale[c], offset[c]) (cpu::decode_u8; default 1/255, 0) and the logits and every tap equal
-  // those of forward() fed the decoded image, bit for bit; chunking and mark as forward(). With the row-band Conv1
-  // on the image (bf16_conv1 2) and Knobs::bf16_u8 that kernel loads the bytes ("u8_ring": no float copy of the
-  // input exists); everywhere else hip::decode_u8 writes the launch chunk as fp32 into a workspace and the float
-  // path runs unchanged ("u8_decode"). The first byte call that needs the workspace allocates it (chunk-sized,
-  // freed with the engine), never inside a stream capture: warm up once before capturing a graph.
-  hipError_t forward_u8(const uint8_t* x, int N, float* logits, hipStream_t s, bool mark = false);
-  void set_input_norm(const float* scale, const float* offset);  // three values each
-  // The classifier head on top of forward / forward_u8: idx int32 [N][k] and prob fp32 [N][k] device, the k most
-  // likely classes of each image and their softmax probabilities (cpu::softmax_topk is the definition; 1 <= k <=
-  // min(classes, kMaxTopK), else hipErrorInvalidValue). logits (nullable): [N,classes] fp32 device, the bits
-  // forward() writes. The same layer chain as forward: chunking (outputs advance by n * k per chunk), mark,
-  // last_input() and last_path() are forward's. Where FC8 went through split-K slabs, the head kernel reduces them
-  // itself with FC8's bias in place of splitk_reduce_bf16 (Knobs::bf16_head; 0: the reduce writes the logits and
-  // the head runs on those); where FC8 writes fp32 directly the head runs on the logits. Logits nobody asked for
-  // go to a workspace the constructor allocated: no call allocates, so a call can be captured into a graph.
-  hipError_t classify(const float* x, int N, int k, int* idx, float* prob, float* logits, hipStream_t s,
-                      bool mark = false);
-  hipError_t classify_u8(const uint8_t* x, int N, int k, int* idx, float* prob, float* logits, hipStream_t s,
-                         bool mark = false);
-  // classify over V views per image: x holds `rows` = N * V images, image-major (row i * V + v is view v of image
-  // i); idx / prob are [rows / V][k], the k best classes of the mean of each image's V softmax rows
-  // (cpu::softmax_topk_views is the definition); logits (nullable): [rows, classes]. The layer chain, mark,
-  // last_input(), last_path() and last_head() are classify's: where FC8 ends in split-K slabs the view kernel takes
-  // them with the bias (Knobs::bf16_head), else it runs on the written logits. A launch chunk holds whole images
-  // (the chunk step is the largest multiple of V images the engine's chunk holds). hipErrorInvalidValue: V outside
-  // 1 .. kMaxViews, rows % V != 0, a chunk smaller than V, more than hip::kSoftmaxViewsMaxK classes, k as
-  // classify. No call allocates.
-  hipError_t classify_views(const float* x, int rows, int V, int k, int* idx, float* prob, float* logits, hipStream_t s,
-                            bool mark = false);
-  hipError_t classify_views_u8(const uint8_t* x, int rows, int V, int k, int* idx, float* prob, float* logits,
-                               hipStream_t s, bool mark = false);
+  // Runs the layer chain as `c` describes (FullCall above): the only way in. hipErrorInvalidValue, before any launch or
+  // event creation, when check(c) gives a reason.
+  hipError_t run(const FullCall& c, hipStream_t s);
+  // Null, or why run() refuses `c` (a static string): the one statement of the limits on k, views, rows and the
+  // pointers (full_engine.cpp), which the C ABI reports word for word.
+  const char* check(const FullCall& c) const;
+  void set_input_norm(const float* scale, const float* offset);  // byte input: three values each
   // What the head of the last call read: "slabs" (it reduced FC8's split-K slabs), "logits" (written logits), null
-  // when the last call was forward / forward_u8. Recorded at the launch from host state.
+  // when the last call had no head (k == 0). Recorded at the launch from host state.
   const char* last_head() const { return head_; }
-  // How the last forward's input reached Conv1: "f32", "u8_ring", "u8_decode"; null before the first. Recorded at
+  // How the last call's input reached Conv1: "f32", "u8_ring", "u8_decode"; null before the first. Recorded at
   // the launch site from host state.
   const char* last_input() const { return input_; }
-  // forward(..., mark = true) records this engine's mark event on `s` once Conv2 + Pool2/LRN of the
-  // first chunk are enqueued (about half of the forward): wait_mark makes another stream wait for it,
-  // which staggers free-running lanes (AlexNetFull.forward_async) by half a forward.
+  // Makes `s` wait for the mark event the last call with FullCall::mark recorded, which staggers free-running lanes
+  // (AlexNetFull.forward_async) by half a forward.
   hipError_t wait_mark(hipStream_t s) const {
     return mark_ ? hipStreamWaitEvent(s, mark_.get(), 0) : hipErrorInvalidValue;
   }
@@ -215,20 +219,14 @@ class FullEngine {
     int key = -1;
     std::vector<float> host;  // KCFF fp32 (re-pack when the tile variant changes)
   };
-  // classify's outputs for the launch chunk at hand; slabs: set by conv() when the head kernel took FC8's slabs
-  struct Head {
-    int k;
-    int* idx;
-    float* prob;
-    float* logits;  // nullable
-    bool slabs;
-    int views = 0;  // classify_views: rows per image (idx / prob then hold one row per image); 0: one row per image
-  };
+  // head: FC8 of a call with a head, the call narrowed to the launch chunk at hand (its rows and outputs). Where the
+  // layer ends in split-K slabs and Knobs::bf16_head is set, run_head() takes them in place of the reduce.
   hipError_t conv(Layer& L, int N, int Hp, int Wp, const void* x, hip::OutViewB out, float* out_f32, bool relu,
-                  hipStream_t s, Head* head = nullptr);
-  // the one layer chain: exactly one of xf (floats) / xu (bytes) is set; head: classify's outputs (whole call)
-  hipError_t run(const float* xf, const uint8_t* xu, int N, float* logits, hipStream_t s, bool mark,
-                 const Head* head = nullptr);
+                  hipStream_t s, const FullCall* head = nullptr);
+  // The head kernel of launch chunk `ch` (views or not) on its rows at src: FC8's ksplit slabs, slab_stride floats
+  // apart, plus bias; or with ksplit 1 and no bias the chunk's written logits. Records last_head().
+  hipError_t run_head(const FullCall& ch, const float* src, int ksplit, size_t slab_stride, const float* bias,
+                      hipStream_t s);
   hip::U8Norm norm_{3, {1.f / 255.f, 1.f / 255.f, 1.f / 255.f}, {0.f, 0.f, 0.f}};  // byte input: scale / offset
   DevBuf<float> xdec_;             // byte input decoded to fp32 (u8_decode), chunk_ images, allocated on first need
   const char* input_ = nullptr;    // last_input()

@@ -146,41 +146,45 @@ int anx_full_weight_sizes(int classes, int groups2, size_t* wn, size_t* bn);
 int anx_full_create(void** out, const float* const* weights, const float* const* biases, int classes,
                     int max_batch, int groups2, int lrn_mode);
 int anx_full_destroy(void* e);
-int anx_full_forward(void* e, const float* x, int N, float* logits, void* stream);
-/* forward that records the engine's mark event half-way (after Conv2 + Pool2/LRN of the first chunk);
-   anx_full_wait_mark makes `stream` wait for the last recorded mark of engine e. */
-int anx_full_forward_mark(void* e, const float* x, int N, float* logits, void* stream);
+/* One call of the model, described by a value (anx::FullCall in anx/bf16_ops.hpp has the full contract). size: set to
+   sizeof(anx_full_call) by the caller. x: [rows,227,227,3] on the device, fp32, or with u8 bytes from any byte
+   address: a byte b of channel c means fmaf((float)b, scale[c], offset[c]) in fp32 (default scale 1/255, offset 0;
+   set_input_norm takes 3 values each) and the results equal those of the float call fed the decoded image, bit for
+   bit. With the row-band Conv1 on the image (knob bf16_conv1 = 2) and knob bf16_u8 = 1 that kernel loads the bytes
+   itself; everywhere else the launch chunk is decoded into a workspace that the first such call allocates (never
+   inside a stream capture: warm up once before capturing). No other call allocates.
+   k = 0, the plain forward: logits [rows][classes] fp32. k in 1 .. min(classes, 16), the classifier head: idx [N][k]
+   int32 and prob [N][k] fp32 on the device, the k most likely classes per image and their probabilities; logits
+   (nullable) as above, the bits the plain forward writes. Knob bf16_head = 1: where FC8 went through split-K slabs
+   the head kernel reduces them itself; 0: the reduce writes the logits first; same bits.
+   views = 0: N = rows, classes ranked by logit descending, then index ascending (anx_softmax_topk). views = V in
+   1 .. 32: x holds rows = N*V images, image-major, and the head is anx_softmax_topk_views (ranked by mean
+   probability, so V = 1 is not views = 0); rows % V == 0, classes <= 7680, and a launch chunk holds whole images:
+   an engine whose chunk is smaller than V refuses the call.
+   mark: record the engine's mark event half-way (after Conv2 + Pool2/LRN of the first chunk); anx_full_wait_mark
+   makes `stream` wait for the last recorded mark of engine e.
+   A malformed call (null c, a wrong size, no engine, a missed limit) is refused with a message before anything is
+   launched. */
+typedef struct anx_full_call {
+  size_t size;
+  const void* x;
+  int u8;
+  int rows;
+  float* logits;
+  int mark;
+  int k;
+  int* idx;
+  float* prob;
+  int views;
+} anx_full_call;
+int anx_full_run(void* e, const anx_full_call* c, void* stream);
 int anx_full_wait_mark(void* e, void* stream);
-/* Byte input ([N,227,227,3] uint8 on the device, from any byte address): a byte b of channel c means
-   fmaf((float)b, scale[c], offset[c]) in fp32 (default scale 1/255, offset 0; set_input_norm takes 3 values each).
-   The _u8 entry points have the contracts of their float twins and give the logits and taps of the float twin fed
-   the decoded image, bit for bit. With the row-band Conv1 on the image (knob bf16_conv1 = 2) and knob bf16_u8 = 1
-   that kernel loads the bytes itself; everywhere else the launch chunk is decoded into a workspace that the first
-   such call allocates (never inside a stream capture: warm up once before capturing). anx_full_last_input writes
-   "f32", "u8_ring" or "u8_decode" (how the last forward fed Conv1; "" before the first) into buf; no device call. */
-int anx_full_forward_u8(void* e, const uint8_t* x, int N, float* logits, void* stream);
-int anx_full_forward_mark_u8(void* e, const uint8_t* x, int N, float* logits, void* stream);
 int anx_full_set_input_norm(void* e, const float* scale, const float* offset);
+/* anx_full_last_input writes "f32", "u8_ring" or "u8_decode" (how the last call fed Conv1; "" before the first) into
+   buf, anx_full_last_head "slabs" or "logits" (what the last call's head read; "" after a plain forward); no device
+   call. */
 int anx_full_last_input(void* e, char* buf, size_t cap);
-/* The classifier head on top of forward / forward_u8 (same chunking, mark, last_input and last_path): idx [N][k]
-   int32 and prob [N][k] fp32 on the device, the k most likely classes per image (value descending, then index
-   ascending) and their softmax probabilities, 1 <= k <= min(classes, 16); logits (nullable) [N][classes] = the
-   bits anx_full_forward writes. Knob bf16_head = 1: where FC8 went through split-K slabs the head kernel reduces
-   them itself; 0: the reduce writes the logits first; same bits. No call allocates. anx_full_last_head writes
-   "slabs" or "logits" (what the last call's head read; "" after a plain forward) into buf; no device call. */
-int anx_full_classify(void* e, const float* x, int N, int k, int* idx, float* prob, float* logits, void* stream,
-                      int mark);
-int anx_full_classify_u8(void* e, const uint8_t* x, int N, int k, int* idx, float* prob, float* logits, void* stream,
-                         int mark);
 int anx_full_last_head(void* e, char* buf, size_t cap);
-/* classify over V views per image: x holds rows = N*V images, image-major; idx / prob are [rows/V][k], the head is
-   anx_softmax_topk_views (on FC8's slabs with knob bf16_head = 1, as above); logits (nullable) [rows][classes].
-   rows % V == 0, 1 <= V <= 32, classes <= 7680. A launch chunk holds whole images; an engine whose chunk is
-   smaller than V refuses the call. No call allocates. */
-int anx_full_classify_views(void* e, const float* x, int rows, int V, int k, int* idx, float* prob, float* logits,
-                            void* stream, int mark);
-int anx_full_classify_views_u8(void* e, const uint8_t* x, int rows, int V, int k, int* idx, float* prob, float* logits,
-                               void* stream, int mark);
 
 /* ---- host engine (same contract as the device engine; V1 / V2 CPU ranks) ---- */
 int anx_cpu_engine_create(void** out, const anx_block_c* b1, const anx_block_c* b2, int H, int W, const float* w1,

@@ -43,7 +43,7 @@ struct Knobs {
                            // 1 = the same on the s2d4 polyphase copy, 0 = s2d4 + the implicit-GEMM tile kernels
   int bf16_pool1 = 1;      // bf16 pool1: 1 = in the Conv1 ring kernel's epilogue (bf16_conv1 2, one workgroup per
                            // image: the 55x55 map never reaches HBM), 0 = Conv1 writes it and maxpool_bf16 reads it
-  int bf16_u8 = 1;         // bf16 byte input (FullEngine::forward_u8) where the row-band Conv1 reads the image (bf16_conv1
+  int bf16_u8 = 1;         // bf16 byte input (FullCall::u8) where the row-band Conv1 reads the image (bf16_conv1
                            // 2): 1 = that kernel loads the bytes itself and decodes them in registers (no float copy
                            // of the input on the device), 0 = the decode kernel into a workspace, then the float
                            // kernel. Same bits either way; every other Conv1 form always decodes first.
@@ -52,7 +52,7 @@ struct Knobs {
                            // byte kernel alone 89.6 us against 59.3 us of decode + 88.2 us of the float kernel behind
                            // it (100.7 us on floats that no decode just wrote); host-fed 1.35 ms as bytes vs 3.48 ms
                            // as floats (profiles/bf16_u8_input/)
-  int bf16_head = 1;       // bf16 classifier head (FullEngine::classify) where FC8 went through split-K slabs: 1 = the
+  int bf16_head = 1;       // bf16 classifier head (FullCall::k > 0) where FC8 went through split-K slabs: 1 = the
                            // head kernel reduces the slabs itself (the logits never reach HBM unless asked for),
                            // 0 = the split-K reduce writes the logits and the head runs on them. Same bits either way
   int conv1_occ = 0;       // cap on the Conv1 Winograd GEMM's workgroups per CU (LDS padding; 0 = none: 4)

@@ -15,29 +15,11 @@
 #include "anx/ops.hpp"
 #include "anx/plan.hpp"
 #include "anx/rng.hpp"
+#include "capi_util.hpp"
 
 namespace {
-thread_local std::string g_err;
-
-int fail(const std::string& m) {
-  g_err = m;
-  return 1;
-}
-int hip_status(hipError_t e, const char* what) {
-  if (e == hipSuccess) return 0;
-  return fail(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-template <class F>
-int guarded(const char* what, F&& f) {
-  try {
-    return f();
-  } catch (const std::exception& ex) {
-    return fail(std::string(what) + ": " + ex.what());
-  } catch (...) {
-    return fail(std::string(what) + ": unknown exception");
-  }
-}
+thread_local std::string g_err;  // what anx_set_last_error keeps and anx_last_error returns
+using namespace anx::capi;       // fail, hip_status, guarded, put_string
 
 anx::BlockSpec from_c(const anx_block_c& b) {
   anx::BlockSpec s{};
@@ -128,7 +110,10 @@ const char* anx_last_error(void) { return g_err.c_str(); }
 // 7: ten views per image: mirrored resize outputs (anx_resize_crop_u8_flip, anx_cpu_resize_crop_u8_flip) and the
 //    view-averaging head (anx_softmax_topk_views, anx_cpu_softmax_topk_views, anx_full_classify_views,
 //    anx_full_classify_views_u8)
-int anx_abi_version(void) { return 7; }
+// 8: one described call of the bf16 full model, anx_full_run(engine, anx_full_call*, stream). REMOVED: the eight
+//    entries it replaces, anx_full_forward, anx_full_forward_mark, anx_full_forward_u8, anx_full_forward_mark_u8,
+//    anx_full_classify, anx_full_classify_u8, anx_full_classify_views, anx_full_classify_views_u8
+int anx_abi_version(void) { return 8; }
 
 int anx_device_live(size_t out[4]) {
   if (!out) return fail("anx_device_live: no buffer");
@@ -281,12 +266,9 @@ int anx_engine_stage1_u8(void* e, const uint8_t* x, int N, const anx_tile_c* t, 
 
 int anx_engine_last_input(void* e, char* buf, size_t cap) {
   return guarded("anx_engine_last_input", [&] {
-    if (!e || !buf || cap == 0) return fail("anx_engine_last_input: no engine or buffer");
+    if (!e) return fail("anx_engine_last_input: no engine");
     const char* v = static_cast<anx::BlocksEngine*>(e)->last_input();
-    const std::string sv = v ? v : "";
-    if (sv.size() + 1 > cap) return fail("anx_engine_last_input: output buffer too small");
-    std::memcpy(buf, sv.c_str(), sv.size() + 1);
-    return 0;
+    return put_string("anx_engine_last_input", v ? v : "", buf, cap);
   });
 }
 
@@ -711,13 +693,6 @@ int anx_rng_uniform(uint64_t seed, uint64_t stream, float* out, size_t n) {
 
 // ---------------------------------------------------------------------------------------- cost model
 namespace {
-int put_json(const std::string& j, char* buf, size_t cap, const char* who = "anx_cost") {
-  if (!buf || cap == 0) return fail(std::string(who) + ": no output buffer");
-  if (j.size() + 1 > cap)
-    return fail(std::string(who) + ": output buffer too small (" + std::to_string(j.size() + 1) + " bytes)");
-  std::memcpy(buf, j.c_str(), j.size() + 1);
-  return 0;
-}
 anx::Workload wl_of(int w) {
   if (w < 0 || w > 2) throw std::invalid_argument("workload must be 0 (dp), 1 (v4) or 2 (v5)");
   return static_cast<anx::Workload>(w);
@@ -728,20 +703,22 @@ extern "C" int anx_cost_curve(int workload, const int* nps, int n_nps, int batch
                               int mode, const char* overrides, char* buf, size_t cap) {
   return guarded("anx_cost_curve", [&] {
     std::vector<int> v(nps, nps + std::max(0, n_nps));
-    return put_json(anx::model_curve_json(wl_of(workload), v, batch, row_ways,
-                                          static_cast<anx::InputSource>(input_source != 0), static_cast<anx::Decomp>(mode),
-                                          anx::cost_params(overrides ? overrides : "")),
-                    buf, cap);
+    return put_string("anx_cost_curve",
+                      anx::model_curve_json(wl_of(workload), v, batch, row_ways,
+                                            static_cast<anx::InputSource>(input_source != 0),
+                                            static_cast<anx::Decomp>(mode), anx::cost_params(overrides ? overrides : "")),
+                      buf, cap);
   });
 }
 
 extern "C" int anx_cost_step(int workload, int np, int batch, int row_ways, int input_source, int mode,
                              const char* overrides, char* buf, size_t cap) {
   return guarded("anx_cost_step", [&] {
-    return put_json(anx::model_step(wl_of(workload), np, batch, row_ways, static_cast<anx::InputSource>(input_source != 0),
-                                    static_cast<anx::Decomp>(mode), anx::cost_params(overrides ? overrides : ""))
-                        .json(),
-                    buf, cap);
+    return put_string("anx_cost_step",
+                      anx::model_step(wl_of(workload), np, batch, row_ways, static_cast<anx::InputSource>(input_source != 0),
+                                      static_cast<anx::Decomp>(mode), anx::cost_params(overrides ? overrides : ""))
+                          .json(),
+                      buf, cap);
   });
 }
 
@@ -770,8 +747,9 @@ extern "C" int anx_engine_last_path(void* e, char* buf, size_t cap) {
     auto field = [](const char* name, const char* v) {
       return std::string("\"") + name + "\": " + (v ? std::string("\"") + v + "\"" : std::string("null"));
     };
-    return put_json("{" + field("conv1", p.conv1) + ", " + field("pool1", p.pool1) + ", " + field("conv2", p.conv2) +
-                        ", " + field("pool2", p.pool2) + "}",
-                    buf, cap, "anx_engine_last_path");
+    return put_string("anx_engine_last_path",
+                      "{" + field("conv1", p.conv1) + ", " + field("pool1", p.pool1) + ", " + field("conv2", p.conv2) +
+                          ", " + field("pool2", p.pool2) + "}",
+                      buf, cap);
   });
 }

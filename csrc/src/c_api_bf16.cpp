@@ -9,26 +9,10 @@
 #include "anx/bf16_ops.hpp"
 #include "anx/c_api.h"
 #include "anx/knobs.hpp"
+#include "capi_util.hpp"
 
 namespace {
-int fail(const std::string& m) {
-  anx_set_last_error(m.c_str());
-  return 1;
-}
-int hip_status(hipError_t e, const char* what) {
-  if (e == hipSuccess) return 0;
-  return fail(std::string(what) + ": " + hipGetErrorString(e));
-}
-template <class F>
-int guarded(const char* what, F&& f) {
-  try {
-    return f();
-  } catch (const std::exception& ex) {
-    return fail(std::string(what) + ": " + ex.what());
-  } catch (...) {
-    return fail(std::string(what) + ": unknown exception");
-  }
-}
+using namespace anx::capi;  // fail, hip_status, guarded, put_string
 hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
 }  // namespace
 
@@ -59,31 +43,17 @@ int anx_full_destroy(void* e) {
   return 0;
 }
 
-int anx_full_forward(void* e, const float* x, int N, float* logits, void* stream) {
-  return guarded("anx_full_forward", [&] {
-    return hip_status(static_cast<anx::FullEngine*>(e)->forward(x, N, logits, S(stream)), "full forward");
-  });
-}
-
-int anx_full_forward_mark(void* e, const float* x, int N, float* logits, void* stream) {
-  return guarded("anx_full_forward_mark", [&] {
-    return hip_status(static_cast<anx::FullEngine*>(e)->forward(x, N, logits, S(stream), true), "full forward");
-  });
-}
-
-int anx_full_forward_u8(void* e, const uint8_t* x, int N, float* logits, void* stream) {
-  return guarded("anx_full_forward_u8", [&] {
-    if (!e) return fail("anx_full_forward_u8: no engine");
-    if (N > 0 && (!x || !logits)) return fail("anx_full_forward_u8: no buffer");
-    return hip_status(static_cast<anx::FullEngine*>(e)->forward_u8(x, N, logits, S(stream)), "full forward (bytes)");
-  });
-}
-
-int anx_full_forward_mark_u8(void* e, const uint8_t* x, int N, float* logits, void* stream) {
-  return guarded("anx_full_forward_mark_u8", [&] {
-    if (!e) return fail("anx_full_forward_mark_u8: no engine");
-    if (N > 0 && (!x || !logits)) return fail("anx_full_forward_mark_u8: no buffer");
-    return hip_status(static_cast<anx::FullEngine*>(e)->forward_u8(x, N, logits, S(stream), true), "full forward (bytes)");
+int anx_full_run(void* e, const anx_full_call* c, void* stream) {
+  return guarded("anx_full_run", [&] {
+    if (!c) return fail("anx_full_run: no call");
+    if (c->size != sizeof(anx_full_call))
+      return fail("anx_full_run: size is " + std::to_string(c->size) + ", sizeof(anx_full_call) is " +
+                  std::to_string(sizeof(anx_full_call)));
+    if (!e) return fail("anx_full_run: no engine");
+    auto* eng = static_cast<anx::FullEngine*>(e);
+    const anx::FullCall call{c->x, c->u8 != 0, c->rows, c->logits, c->mark != 0, c->k, c->idx, c->prob, c->views};
+    if (const char* why = eng->check(call)) return fail(std::string("anx_full_run: ") + why);
+    return hip_status(eng->run(call, S(stream)), "anx_full_run");
   });
 }
 
@@ -96,82 +66,12 @@ int anx_full_set_input_norm(void* e, const float* scale, const float* offset) {
   });
 }
 
-// How the last forward's input reached Conv1 ("" before the first). Host state only.
+// How the last call's input reached Conv1 ("" before the first). Host state only.
 int anx_full_last_input(void* e, char* buf, size_t cap) {
   return guarded("anx_full_last_input", [&] {
     if (!e) return fail("anx_full_last_input: no engine");
-    if (!buf || cap == 0) return fail("anx_full_last_input: no buffer");
     const char* v = static_cast<anx::FullEngine*>(e)->last_input();
-    const std::string j = v ? v : "";
-    if (j.size() + 1 > cap) return fail("anx_full_last_input: buffer too small");
-    j.copy(buf, j.size());
-    buf[j.size()] = 0;
-    return 0;
-  });
-}
-
-namespace {
-// the argument checks of the two classify entries; 0 = fine
-int classify_args(const std::string& fn, void* e, const void* x, int N, int k, const int* idx, const float* prob) {
-  if (!e) return fail(fn + ": no engine");
-  const int classes = static_cast<anx::FullEngine*>(e)->classes();
-  if (k < 1 || k > anx::cpu::kMaxTopK || k > classes)
-    return fail(fn + ": 1 <= k <= min(classes, 16), got k = " + std::to_string(k) + " for " + std::to_string(classes) +
-                " classes");
-  if (N > 0 && (!x || !idx || !prob)) return fail(fn + ": no buffer (x, idx, prob)");
-  return 0;
-}
-}  // namespace
-
-int anx_full_classify(void* e, const float* x, int N, int k, int* idx, float* prob, float* logits, void* stream,
-                      int mark) {
-  return guarded("anx_full_classify", [&] {
-    if (classify_args("anx_full_classify", e, x, N, k, idx, prob)) return 1;
-    return hip_status(static_cast<anx::FullEngine*>(e)->classify(x, N, k, idx, prob, logits, S(stream), mark != 0),
-                      "anx_full_classify");
-  });
-}
-
-int anx_full_classify_u8(void* e, const uint8_t* x, int N, int k, int* idx, float* prob, float* logits, void* stream,
-                         int mark) {
-  return guarded("anx_full_classify_u8", [&] {
-    if (classify_args("anx_full_classify_u8", e, x, N, k, idx, prob)) return 1;
-    return hip_status(static_cast<anx::FullEngine*>(e)->classify_u8(x, N, k, idx, prob, logits, S(stream), mark != 0),
-                      "anx_full_classify_u8");
-  });
-}
-
-namespace {
-// what the two classify_views entries check beyond classify_args; 0 = fine
-int views_args(const std::string& fn, void* e, int rows, int V) {
-  if (V < 1 || V > anx::cpu::kMaxViews) return fail(fn + ": 1 <= V <= 32 views, got " + std::to_string(V));
-  if (rows < 0 || rows % V != 0)
-    return fail(fn + ": " + std::to_string(rows) + " rows are no whole number of images of " + std::to_string(V) + " views");
-  if (static_cast<anx::FullEngine*>(e)->classes() > anx::hip::kSoftmaxViewsMaxK)
-    return fail(fn + ": more than " + std::to_string(anx::hip::kSoftmaxViewsMaxK) + " classes");
-  return 0;
-}
-}  // namespace
-
-int anx_full_classify_views(void* e, const float* x, int rows, int V, int k, int* idx, float* prob, float* logits,
-                            void* stream, int mark) {
-  return guarded("anx_full_classify_views", [&] {
-    if (classify_args("anx_full_classify_views", e, x, rows, k, idx, prob)) return 1;
-    if (views_args("anx_full_classify_views", e, rows, V)) return 1;
-    return hip_status(
-        static_cast<anx::FullEngine*>(e)->classify_views(x, rows, V, k, idx, prob, logits, S(stream), mark != 0),
-        "anx_full_classify_views");
-  });
-}
-
-int anx_full_classify_views_u8(void* e, const uint8_t* x, int rows, int V, int k, int* idx, float* prob, float* logits,
-                               void* stream, int mark) {
-  return guarded("anx_full_classify_views_u8", [&] {
-    if (classify_args("anx_full_classify_views_u8", e, x, rows, k, idx, prob)) return 1;
-    if (views_args("anx_full_classify_views_u8", e, rows, V)) return 1;
-    return hip_status(
-        static_cast<anx::FullEngine*>(e)->classify_views_u8(x, rows, V, k, idx, prob, logits, S(stream), mark != 0),
-        "anx_full_classify_views_u8");
+    return put_string("anx_full_last_input", v ? v : "", buf, cap);
   });
 }
 
@@ -179,13 +79,8 @@ int anx_full_classify_views_u8(void* e, const uint8_t* x, int rows, int V, int k
 int anx_full_last_head(void* e, char* buf, size_t cap) {
   return guarded("anx_full_last_head", [&] {
     if (!e) return fail("anx_full_last_head: no engine");
-    if (!buf || cap == 0) return fail("anx_full_last_head: no buffer");
     const char* v = static_cast<anx::FullEngine*>(e)->last_head();
-    const std::string j = v ? v : "";
-    if (j.size() + 1 > cap) return fail("anx_full_last_head: buffer too small");
-    j.copy(buf, j.size());
-    buf[j.size()] = 0;
-    return 0;
+    return put_string("anx_full_last_head", v ? v : "", buf, cap);
   });
 }
 
@@ -203,7 +98,6 @@ int anx_full_tap(void* e, int i, int N, void* dst, size_t* elems, void* stream) 
 int anx_full_last_path(void* e, char* buf, size_t cap) {
   return guarded("anx_full_last_path", [&] {
     if (!e) return fail("anx_full_last_path: no engine");
-    if (!buf || cap == 0) return fail("anx_full_last_path: no buffer");
     const anx::FullPathRecord& p = static_cast<anx::FullEngine*>(e)->last_path();
     std::string j = "{\"conv1\": ";
     if (p.conv1)
@@ -221,11 +115,7 @@ int anx_full_last_path(void* e, char* buf, size_t cap) {
       else
         j += "null";
     }
-    j += "}";
-    if (j.size() + 1 > cap) return fail("anx_full_last_path: buffer too small (" + std::to_string(j.size() + 1) + " bytes)");
-    j.copy(buf, j.size());
-    buf[j.size()] = 0;
-    return 0;
+    return put_string("anx_full_last_path", j + "}", buf, cap);
   });
 }
 int anx_full_set_knob(void* e, const char* name, int value) {

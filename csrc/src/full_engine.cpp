@@ -105,7 +105,7 @@ FullEngine::FullEngine(const FullWeights& w, int classes, int max_batch, int gro
 }
 
 hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip::OutViewB out, float* out_f32,
-                            bool relu, hipStream_t s, Head* head) {
+                            bool relu, hipStream_t s, const FullCall* head) {
   auto B = [](void* q) { return static_cast<__bf16*>(q); };
   const hip::ConvPlanB p = hip::make_conv_plan_bf16(N, Hp, Wp, L.C, L.K, L.F, L.S, L.groups);
   if (p.variant != L.key) {  // pack for this tile variant (first use / batch-size class change)
@@ -137,18 +137,9 @@ hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip:
     rec.splitk = ksplit;
     return e;
   };
-  // classify with bf16_head: the head kernel reduces the slabs [ksplit][N][K] (+ bias) in place of the reduce. A row
-  // too long for its LDS is staged in the logits buffer, which out_f32 always is under classify.
+  // a call with a head and bf16_head: the head kernel reduces the slabs [ksplit][N][K] (+ bias) in place of the reduce
   auto reduce = [&](int ksplit) {
-    if (head && k_.bf16_head) {
-      head->slabs = true;
-      if (head->views)  // N rows = N / views images
-        return hip::softmax_topk_views(ws_.get(), ksplit, static_cast<size_t>(N) * L.K, L.bias.get(), N / head->views,
-                                       head->views, L.K, head->k, head->idx, head->prob, nullptr, head->logits, s);
-      float* lo = head->logits ? head->logits : L.K > hip::kSoftmaxTopkLdsRow ? out_f32 : nullptr;
-      return hip::softmax_topk(ws_.get(), ksplit, static_cast<size_t>(N) * L.K, L.bias.get(), N, L.K, head->k, head->idx,
-                               head->prob, lo, s);
-    }
+    if (head && k_.bf16_head) return run_head(*head, ws_.get(), ksplit, static_cast<size_t>(N) * L.K, L.bias.get(), s);
     return hip::splitk_reduce_bf16(ws_.get(), ksplit, N, L.K, L.bias.get(), relu, out, out_f32, s);
   };
   if (fc && k_.bf16_big != -2) {  // wide-tile FC: one 256-row tile of the batch, K split over the CUs
@@ -176,55 +167,46 @@ hipError_t FullEngine::conv(Layer& L, int N, int Hp, int Wp, const void* x, hip:
   return tile(1, hip::conv2d_bf16(p, x, L.wp.get(), L.koff.get(), L.bias.get(), out, out_f32, relu, s, {}, k_.bf16_glds, &rec.id));
 }
 
-hipError_t FullEngine::forward(const float* x, int N, float* logits, hipStream_t s, bool mark) {
-  return run(x, nullptr, N, logits, s, mark);
-}
-
-hipError_t FullEngine::forward_u8(const uint8_t* x, int N, float* logits, hipStream_t s, bool mark) {
-  return run(nullptr, x, N, logits, s, mark);
-}
-
-hipError_t FullEngine::classify(const float* x, int N, int k, int* idx, float* prob, float* logits, hipStream_t s,
-                                bool mark) {
-  const Head h{k, idx, prob, logits, false};
-  return run(x, nullptr, N, logits, s, mark, &h);
-}
-
-hipError_t FullEngine::classify_u8(const uint8_t* x, int N, int k, int* idx, float* prob, float* logits, hipStream_t s,
-                                   bool mark) {
-  const Head h{k, idx, prob, logits, false};
-  return run(nullptr, x, N, logits, s, mark, &h);
-}
-
-hipError_t FullEngine::classify_views(const float* x, int rows, int V, int k, int* idx, float* prob, float* logits,
-                                      hipStream_t s, bool mark) {
-  if (V < 1) return hipErrorInvalidValue;  // 0 would mean classify
-  const Head h{k, idx, prob, logits, false, V};
-  return run(x, nullptr, rows, logits, s, mark, &h);
-}
-
-hipError_t FullEngine::classify_views_u8(const uint8_t* x, int rows, int V, int k, int* idx, float* prob, float* logits,
-                                         hipStream_t s, bool mark) {
-  if (V < 1) return hipErrorInvalidValue;
-  const Head h{k, idx, prob, logits, false, V};
-  return run(nullptr, x, rows, logits, s, mark, &h);
-}
-
 void FullEngine::set_input_norm(const float* scale, const float* offset) {
   for (int c = 0; c < 3; ++c) norm_.sc[c] = scale[c], norm_.of[c] = offset[c];
 }
 
-hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* logits, hipStream_t s, bool mark,
-                           const Head* head) {
-  if (head && (head->k < 1 || head->k > cpu::kMaxTopK || head->k > classes_ || (N > 0 && (!head->idx || !head->prob))))
-    return hipErrorInvalidValue;
-  // views: whole images per launch chunk
-  const int V = head ? head->views : 0;
-  if (V && (V > cpu::kMaxViews || N % V != 0 || chunk_ < V || classes_ > hip::kSoftmaxViewsMaxK))
-    return hipErrorInvalidValue;
-  const int step = V ? chunk_ / V * V : chunk_;
+const char* FullEngine::check(const FullCall& c) const {
+  static_assert(cpu::kMaxTopK == 16 && cpu::kMaxViews == 32 && hip::kSoftmaxViewsMaxK == 7680, "the reasons spell them");
+  if (c.rows < 0) return "rows < 0";
+  if (c.k < 0 || c.k > cpu::kMaxTopK || c.k > classes_) return "k outside 0 .. min(classes, 16)";
+  if (c.k == 0 && (c.idx || c.prob || c.views != 0)) return "idx, prob and views go with a head (k > 0)";
+  if (c.rows > 0 && !c.x) return "no input (x)";
+  if (c.rows > 0 && (c.k ? !c.idx || !c.prob : !c.logits)) return c.k ? "no output (idx, prob)" : "no output (logits)";
+  if (c.views < 0 || c.views > cpu::kMaxViews) return "views outside 0 .. 32";
+  if (c.views && c.rows % c.views != 0) return "rows are no whole number of images of `views` views";
+  if (c.views && chunk_ < c.views) return "the engine's launch chunk is smaller than one image's views";
+  if (c.views && classes_ > hip::kSoftmaxViewsMaxK) return "the view-averaging head takes at most 7680 classes";
+  return nullptr;
+}
+
+hipError_t FullEngine::run_head(const FullCall& ch, const float* src, int ksplit, size_t slab_stride, const float* bias,
+                                hipStream_t s) {
+  float* const z = ch.logits ? ch.logits : hlog_.get();  // where the chunk's logits are, or would be
+  const bool slabs = src != z;                           // else they are written: nothing to write again
+  if (ch.views)
+    ANX_TRY(hip::softmax_topk_views(src, ksplit, slab_stride, bias, ch.rows / ch.views, ch.views, classes_, ch.k, ch.idx,
+                                    ch.prob, nullptr, slabs ? ch.logits : nullptr, s));
+  else  // a row too long for the kernel's LDS is staged in z (written logits are read back from there)
+    ANX_TRY(hip::softmax_topk(src, ksplit, slab_stride, bias, ch.rows, classes_, ch.k, ch.idx, ch.prob,
+                              slabs && ch.logits ? ch.logits : classes_ > hip::kSoftmaxTopkLdsRow ? z : nullptr, s));
+  head_ = slabs ? "slabs" : "logits";
+  return hipSuccess;
+}
+
+hipError_t FullEngine::run(const FullCall& c, hipStream_t s) {
+  if (check(c)) return hipErrorInvalidValue;
+  const int N = c.rows, V = c.views;
+  const float* const xf = c.u8 ? nullptr : static_cast<const float*>(c.x);
+  const uint8_t* const xu = c.u8 ? static_cast<const uint8_t*>(c.x) : nullptr;
+  const int step = V ? chunk_ / V * V : chunk_;  // views: whole images per launch chunk
   head_ = nullptr;
-  if (mark && !mark_) ANX_TRY(mark_.try_create(hipEventDisableTiming));
+  if (c.mark && !mark_) ANX_TRY(mark_.try_create(hipEventDisableTiming));
   using hip::OutViewB;
   auto B = [](void* p) { return static_cast<__bf16*>(p); };
   constexpr size_t kImage = 227 * 227 * 3;
@@ -284,30 +266,27 @@ hipError_t FullEngine::run(const float* xf, const uint8_t* xu, int N, float* log
     ANX_TRY(conv(L_[1], n, 31, 31, q2_, OutViewB{B(c2_), 27, 27, 256, 0, 0, 0}, nullptr, true, s));
     ANX_TRY(hip::maxpool_lrn_bf16(c2_, n, 27, 27, 256, 3, 2, 5, 1e-4f, 0.75f, 2.0f, lrn_,
                                   OutViewB{B(q3_), 15, 15, 256, 1, 1, 0}, s, k_.bf16_lrn_tile));
-    if (mark && n0 == 0) ANX_TRY(hipEventRecord(mark_.get(), s));
+    if (c.mark && n0 == 0) ANX_TRY(hipEventRecord(mark_.get(), s));
     ANX_TRY(conv(L_[2], n, 15, 15, q3_, OutViewB{B(q4_), 15, 15, 384, 1, 1, 0}, nullptr, true, s));
     ANX_TRY(conv(L_[3], n, 15, 15, q4_, OutViewB{B(q5_), 15, 15, 384, 1, 1, 0}, nullptr, true, s));
     ANX_TRY(conv(L_[4], n, 15, 15, q5_, OutViewB{B(c5_), 13, 13, 256, 0, 0, 0}, nullptr, true, s));
     ANX_TRY(hip::maxpool_bf16(c5_, n, 13, 13, 256, 3, 2, OutViewB{B(f6_), 6, 6, 256, 0, 0, 0}, s));
     ANX_TRY(conv(L_[5], n, 1, 1, f6_, OutViewB{B(f7_), 1, 1, 4096, 0, 0, 0}, nullptr, true, s));
     ANX_TRY(conv(L_[6], n, 1, 1, f7_, OutViewB{B(f8_), 1, 1, 4096, 0, 0, 0}, nullptr, true, s));
-    if (!head) {
-      ANX_TRY(conv(L_[7], n, 1, 1, f8_, OutViewB{nullptr, 1, 1, classes_, 0, 0, 0},
-                   logits + static_cast<size_t>(n0) * classes_, false, s));
-      continue;
+    // FC8 and the head on this chunk: the call narrowed to its rows and outputs (one output row per image). Logits the
+    // caller does not take go to the workspace.
+    FullCall ch = c;
+    ch.rows = n;
+    if (c.logits) ch.logits = c.logits + static_cast<size_t>(n0) * classes_;
+    if (c.k) {
+      const size_t o0 = static_cast<size_t>(V ? n0 / V : n0) * c.k;
+      ch.idx = c.idx + o0;
+      ch.prob = c.prob + o0;
     }
-    // classify: this chunk's outputs; logits the caller does not take go to the workspace
-    const size_t o0 = static_cast<size_t>(V ? n0 / V : n0) * head->k;  // outputs: one row per image
-    Head h{head->k, head->idx + o0, head->prob + o0, logits ? logits + static_cast<size_t>(n0) * classes_ : nullptr,
-           false, V};
-    float* const z = h.logits ? h.logits : hlog_.get();
-    ANX_TRY(conv(L_[7], n, 1, 1, f8_, OutViewB{nullptr, 1, 1, classes_, 0, 0, 0}, z, false, s, &h));
-    if (!h.slabs && V)
-      ANX_TRY(hip::softmax_topk_views(z, 1, 0, nullptr, n / V, V, classes_, h.k, h.idx, h.prob, nullptr, nullptr, s));
-    else if (!h.slabs)  // on the written logits (a row too long for the head's LDS is read back from them)
-      ANX_TRY(hip::softmax_topk(z, 1, 0, nullptr, n, classes_, h.k, h.idx, h.prob,
-                                classes_ > hip::kSoftmaxTopkLdsRow ? z : nullptr, s));
-    head_ = h.slabs ? "slabs" : "logits";
+    float* const z = ch.logits ? ch.logits : hlog_.get();
+    head_ = nullptr;
+    ANX_TRY(conv(L_[7], n, 1, 1, f8_, OutViewB{nullptr, 1, 1, classes_, 0, 0, 0}, z, false, s, c.k ? &ch : nullptr));
+    if (c.k && !head_) ANX_TRY(run_head(ch, z, 1, 0, nullptr, s));  // FC8 wrote the logits: the head runs on those
   }
   return hipSuccess;
 }

@@ -8,6 +8,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "../capi_util.hpp"
 #include "anx/c_api.h"
 #include "anx/v4.hpp"
 #include "anx/v5.hpp"
@@ -19,17 +20,7 @@ struct V5Handle {
   std::unique_ptr<anx::V5Runtime> rt;  // destroyed first (its teardown is collective over comm)
 };
 
-template <class F>
-int guarded(const char* what, F&& f) {
-  try {
-    return f();
-  } catch (const std::exception& ex) {
-    anx_set_last_error((std::string(what) + ": " + ex.what()).c_str());
-  } catch (...) {
-    anx_set_last_error((std::string(what) + ": unknown exception").c_str());
-  }
-  return 1;
-}
+using anx::capi::guarded;
 
 anx::BlockSpec spec(const anx_block_c& b) {
   anx::BlockSpec s{};

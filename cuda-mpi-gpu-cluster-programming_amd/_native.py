@@ -47,6 +47,15 @@ class XferC(C.Structure):
     _fields_ = [("src", C.c_int), ("dst", C.c_int), ("lo", C.c_int), ("hi", C.c_int)]
 
 
+class FullCallC(C.Structure):
+    """anx_full_call: one call of the bf16 full model (``size`` is filled in; ``k`` 0 is the plain forward)."""
+    _fields_ = [("size", C.c_size_t), ("x", C.c_void_p), ("u8", C.c_int), ("rows", C.c_int), ("logits", C.c_void_p),
+                ("mark", C.c_int), ("k", C.c_int), ("idx", C.c_void_p), ("prob", C.c_void_p), ("views", C.c_int)]
+
+    def __init__(self, **fields):
+        super().__init__(size=C.sizeof(FullCallC), **fields)
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -171,22 +180,15 @@ _BF16_SIGS = {
     "anx_full_weight_sizes": (_I, [_I, _I, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "anx_full_create": (_I, [C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _I, _I, _I, _I]),
     "anx_full_destroy": (_I, [_P]),
-    "anx_full_forward": (_I, [_P, _P, _I, _P, _P]),
-    "anx_full_forward_mark": (_I, [_P, _P, _I, _P, _P]),
+    "anx_full_run": (_I, [_P, C.POINTER(FullCallC), _P]),
     "anx_full_wait_mark": (_I, [_P, _P]),
     "anx_full_set_knob": (_I, [_P, C.c_char_p, _I]),
     "anx_full_tap": (_I, [_P, _I, _I, _P, C.POINTER(_SZ), _P]),
     "anx_full_get_knob": (_I, [_P, C.c_char_p, C.POINTER(_I)]),
     "anx_full_last_path": (_I, [_P, C.c_char_p, _SZ]),
-    "anx_full_forward_u8": (_I, [_P, _P, _I, _P, _P]),
-    "anx_full_forward_mark_u8": (_I, [_P, _P, _I, _P, _P]),
     "anx_full_set_input_norm": (_I, [_P, _P, _P]),
     "anx_full_last_input": (_I, [_P, C.c_char_p, _SZ]),
-    "anx_full_classify": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I]),
-    "anx_full_classify_u8": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I]),
     "anx_full_last_head": (_I, [_P, C.c_char_p, _SZ]),
-    "anx_full_classify_views": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I]),
-    "anx_full_classify_views_u8": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I]),
 }
 _bf16 = None
 

@@ -24,6 +24,7 @@ kernel averages the views' softmax outputs on chip (:func:`anx.ops.softmax_topk_
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -61,6 +62,15 @@ def init_full_weights(seed: int = 0, classes: int = 1000, groups2: int = 1) -> d
         out["w_" + name] = torch.from_numpy(((u * 2 - 1) * bound).astype(np.float32).reshape(s))
         out["b_" + name] = torch.zeros(bsz[i])
     return out
+
+
+class _Head(NamedTuple):
+    """The classifier head of a call: ``indices`` / ``probs`` ``[N,k]`` outputs; ``views`` rows of ``x`` per image for
+    the view-averaging head, 0 for one row per image ranked by logit (``views=1`` is not 0: it ranks by probability)."""
+    k: int
+    idx: torch.Tensor
+    prob: torch.Tensor
+    views: int = 0
 
 
 class AlexNetFull:
@@ -202,41 +212,27 @@ class AlexNetFull:
         return out
 
     def _launch(self, x, z, head, stream, mark: bool) -> None:
-        """This engine's one native call on images ``x`` (the only place that names the entry points): the forward
-        into logits ``z``, or with ``head = (k, indices, probs)`` the classify call (``z`` may be None). ``stream``
-        None: the current stream. ``mark``: record the mid-forward mark that ``anx_full_wait_mark`` waits for."""
-        u8 = x.dtype == torch.uint8
-        if stream is None:
-            stream = nat.stream_ptr(self.device)
-        if head is None:
-            if mark:
-                fn = "anx_full_forward_mark_u8" if u8 else "anx_full_forward_mark"
-            else:
-                fn = "anx_full_forward_u8" if u8 else "anx_full_forward"
-            nat.call(fn, self._h, x.data_ptr(), x.shape[0], z.data_ptr(), stream)
-        elif len(head) == 3:
-            k, idx, prob = head
-            nat.call("anx_full_classify_u8" if u8 else "anx_full_classify", self._h, x.data_ptr(), x.shape[0], k,
-                     idx.data_ptr(), prob.data_ptr(), z.data_ptr() if z is not None else None, stream, int(mark))
-        else:  # views: x holds V rows per row of idx / prob
-            k, idx, prob, V = head
-            nat.call("anx_full_classify_views_u8" if u8 else "anx_full_classify_views", self._h, x.data_ptr(),
-                     x.shape[0], V, k, idx.data_ptr(), prob.data_ptr(), z.data_ptr() if z is not None else None, stream,
-                     int(mark))
+        """This engine's one native call on images ``x`` (the only place that names the entry point): the forward
+        into logits ``z``, or with a :class:`_Head` the classify call (``z`` may be None). ``stream`` None: the current
+        stream. ``mark``: record the mid-forward mark that ``anx_full_wait_mark`` waits for."""
+        call = nat.FullCallC(x=x.data_ptr(), u8=int(x.dtype == torch.uint8), rows=x.shape[0],
+                             logits=z.data_ptr() if z is not None else None, mark=int(mark))
+        if head is not None:
+            call.k, call.idx, call.prob, call.views = head.k, head.idx.data_ptr(), head.prob.data_ptr(), head.views
+        nat.call("anx_full_run", self._h, C.byref(call), stream if stream is not None else nat.stream_ptr(self.device))
 
     def _run(self, x, z, head, free: bool = False, pre_lane=None, on_lane=None) -> None:
         """:meth:`_launch` of every lane's slice through :mod:`anx.models.lanes`: forked and joined within the
-        call, or (``free``) left running on the lanes' streams until :meth:`join`. A head with views
-        ``(k, indices, probs, V)`` splits on image boundaries: the lanes divide the ``N`` images, and image ``i`` is
-        rows ``i V .. (i + 1) V`` of ``x`` and ``z``."""
-        views = tuple(head[3:]) if head is not None else ()
-        V = views[0] if views else 1
+        call, or (``free``) left running on the lanes' streams until :meth:`join`. A head with views splits on image
+        boundaries: the lanes divide the ``N`` images, and image ``i`` is rows ``i V .. (i + 1) V`` of ``x`` and
+        ``z``."""
+        V = (head.views if head is not None else 0) or 1
 
         def run(i, lo, hi, st=None, lead=False):
             eng = self._lane(i)
             eng._ensure((hi - lo) * V)
             eng._launch(x[lo * V:hi * V], z[lo * V:hi * V] if z is not None else None,
-                        (head[0], head[1][lo:hi], head[2][lo:hi], *views) if head is not None else None,
+                        head._replace(idx=head.idx[lo:hi], prob=head.prob[lo:hi]) if head is not None else None,
                         st.cuda_stream if st is not None else None, lead)
             if lead:
                 return lambda s: nat.call("anx_full_wait_mark", eng._h, s.cuda_stream)
@@ -248,22 +244,26 @@ class AlexNetFull:
         else:
             self._streams.run_joined(x.shape[0] // V, run)
 
-    def _check_views(self, x, views) -> int | None:
-        """``views`` of :meth:`classify`: None, or the rows per image of ``x``."""
+    def _check_views(self, x, views) -> int:
+        """``views`` of :meth:`classify` as the head takes it: 0 for None, else the rows per image of ``x``."""
+        from ..ops import MAX_VIEWS, VIEWS_MAX_CLASSES
         if views is None:
-            return None
-        if not isinstance(views, int) or isinstance(views, bool) or not 1 <= views <= 32:
-            raise ValueError(f"views must be None or an integer 1 .. 32, got {views!r}")
+            return 0
+        if not isinstance(views, int) or isinstance(views, bool) or not 1 <= views <= MAX_VIEWS:
+            raise ValueError(f"views must be None or an integer 1 .. {MAX_VIEWS}, got {views!r}")
         if x.shape[0] % views:
             raise ValueError(f"{x.shape[0]} rows are no whole number of images of {views} views")
-        if self.classes > 7680:
-            raise ValueError("the view-averaging head takes at most 7680 classes")
+        if self.classes > VIEWS_MAX_CLASSES:
+            raise ValueError(f"the view-averaging head takes at most {VIEWS_MAX_CLASSES} classes")
         return views
 
-    def _check_head(self, x, k, idx, prob, views=None):
-        """classify's outputs: validated like ``out`` in :meth:`_check`, allocated when not given."""
-        if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= min(self.classes, 16):
-            raise ValueError(f"k must be an integer with 1 <= k <= min(classes, 16) = {min(self.classes, 16)}, got {k!r}")
+    def _check_head(self, x, k, idx, prob, views=0) -> _Head:
+        """classify's head: ``k`` checked, the outputs validated like ``out`` in :meth:`_check`, allocated when not
+        given."""
+        from ..ops import MAX_TOPK
+        kmax = min(self.classes, MAX_TOPK)
+        if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= kmax:
+            raise ValueError(f"k must be an integer with 1 <= k <= min(classes, {MAX_TOPK}) = {kmax}, got {k!r}")
         shape = (x.shape[0] // (views or 1), k)
         outs = []
         for t, dt, name in ((idx, torch.int32, "indices"), (prob, torch.float32, "probabilities")):
@@ -273,7 +273,7 @@ class AlexNetFull:
                 raise ValueError(f"{name} must be a contiguous {dt} {shape} tensor on {self.device}, got "
                                  f"{tuple(t.shape)} {t.dtype} on {t.device}")
             outs.append(t)
-        return outs
+        return _Head(k, *outs, views)
 
     def classify(self, x: torch.Tensor, k: int = 5, *, views: int | None = None, return_logits: bool = False, out=None):
         """x as in :meth:`forward` -> ``(indices [N,k] int32, probs [N,k] fp32)``: the ``k`` most likely classes of
@@ -295,9 +295,9 @@ class AlexNetFull:
         self._check_x(x)
         views = self._check_views(x, views)
         z = self._check(x, out[2] if len(out) == 3 else None) if want_logits else None
-        idx, prob = self._check_head(x, k, *(out[:2] if out else (None, None)), views)
-        self._run(x, z, (k, idx, prob) if views is None else (k, idx, prob, views))
-        return (idx, prob, z) if want_logits else (idx, prob)
+        head = self._check_head(x, k, *(out[:2] if out else (None, None)), views)
+        self._run(x, z, head)
+        return (head.idx, head.prob, z) if want_logits else (head.idx, head.prob)
 
     def _preprocess(self, images, resize, views=None) -> torch.Tensor:
         """``images`` (as :func:`anx.ops.resize_crop_u8` takes them) -> ``uint8 [N,227,227,3]`` in the model-owned
@@ -361,11 +361,9 @@ class AlexNetFull:
         writes ``idx_out`` ``[N,k]`` int32 and ``prob_out`` ``[N,k]`` fp32. :meth:`join` before reading them.
         ``views`` as in :meth:`classify` (the hooks then get image bounds, not row bounds)."""
         self._check_x(x)
-        views = self._check_views(x, views)
-        idx_out, prob_out = self._check_head(x, k, idx_out, prob_out, views)
-        self._run(x, None, (k, idx_out, prob_out) if views is None else (k, idx_out, prob_out, views), True, pre_lane,
-                  on_lane)
-        return idx_out, prob_out
+        head = self._check_head(x, k, idx_out, prob_out, self._check_views(x, views))
+        self._run(x, None, head, True, pre_lane, on_lane)
+        return head.idx, head.prob
 
     def last_head(self, lane: int = 0) -> str | None:
         """What the head of the last call of this model's engine (``lane`` > 0: that side lane's) read: ``"slabs"``

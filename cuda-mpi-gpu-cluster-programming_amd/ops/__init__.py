@@ -338,8 +338,37 @@ def resize_crop_u8(images, size=227, resize: int | None = 256, boxes=None, out: 
     return out
 
 
-MAX_TOPK = 16          # kMaxTopK (anx/ops.hpp)
-_HEAD_LDS_ROW = 15 * 1024  # kSoftmaxTopkLdsRow: a longer row is staged in the logits output on the GPU
+MAX_TOPK = 16               # kMaxTopK (anx/ops.hpp)
+MAX_VIEWS = 32              # kMaxViews (anx/ops.hpp)
+VIEWS_MAX_CLASSES = 7680    # kSoftmaxViewsMaxK: two rows of the view-averaging head in LDS on the GPU
+_HEAD_LDS_ROW = 15 * 1024   # kSoftmaxTopkLdsRow: a longer row is staged in the logits output on the GPU
+
+
+def _head_source(fn: str, rows: str, logits, slabs, bias, k):
+    """What both heads take: ``logits`` ``[rows,K]`` or ``slabs`` ``[ksplit,rows,K]`` (+ ``bias`` ``[K]``) and ``k``,
+    checked. Returns ``(src, ksplit, M, K, k)``; ``fn`` and ``rows`` (how ``fn`` names the row count) go into the
+    messages."""
+    if (logits is None) == (slabs is None):
+        raise ValueError(f"{fn}: give logits [{rows},K] or slabs [ksplit,{rows},K], not both")
+    src = logits if slabs is None else slabs
+    _check(src, fn)
+    if slabs is None:
+        if src.dim() != 2:
+            raise ValueError(f"{fn}: logits must be [{rows},K]")
+        if bias is not None:
+            raise ValueError(f"{fn}: a bias goes with slabs")
+        ksplit, (M, K) = 1, src.shape
+    else:
+        if src.dim() != 3 or src.shape[0] < 1:
+            raise ValueError(f"{fn}: slabs must be [ksplit,{rows},K] with ksplit >= 1")
+        ksplit, M, K = src.shape
+    if K < 1 or not 1 <= int(k) <= min(K, MAX_TOPK):
+        raise ValueError(f"{fn}: need 1 <= k <= min(K, {MAX_TOPK}), got k = {k} for K = {K}")
+    if bias is not None:
+        _check(bias, f"{fn} bias")
+        if tuple(bias.shape) != (K,) or bias.device != src.device:
+            raise ValueError(f"{fn}: bias must be [K] on the source's device")
+    return src, ksplit, M, K, int(k)
 
 
 def softmax_topk(logits: torch.Tensor | None = None, k: int = 5, *, slabs: torch.Tensor | None = None,
@@ -353,27 +382,7 @@ def softmax_topk(logits: torch.Tensor | None = None, k: int = 5, *, slabs: torch
     ``-0.0`` and ``+0.0`` tie. ``p = exp(z - max) / sum(exp(z - max))`` in fp32. ``1 <= k <= min(K, 16)``. A row that
     holds a NaN or whose maximum is infinite still gets ``k`` distinct indices; its probabilities are unspecified.
     The host function ``cpu::softmax_topk`` (CPU tensors) is the definition the GPU kernel is tested against."""
-    if (logits is None) == (slabs is None):
-        raise ValueError("softmax_topk: give logits [M,K] or slabs [ksplit,M,K], not both")
-    src = logits if slabs is None else slabs
-    _check(src, "softmax_topk")
-    if slabs is None:
-        if src.dim() != 2:
-            raise ValueError("softmax_topk: logits must be [M,K]")
-        if bias is not None:
-            raise ValueError("softmax_topk: a bias goes with slabs")
-        ksplit, (M, K) = 1, src.shape
-    else:
-        if src.dim() != 3 or src.shape[0] < 1:
-            raise ValueError("softmax_topk: slabs must be [ksplit,M,K] with ksplit >= 1")
-        ksplit, M, K = src.shape
-    if K < 1 or not 1 <= int(k) <= min(K, MAX_TOPK):
-        raise ValueError(f"softmax_topk: need 1 <= k <= min(K, {MAX_TOPK}), got k = {k} for K = {K}")
-    if bias is not None:
-        _check(bias, "softmax_topk bias")
-        if tuple(bias.shape) != (K,) or bias.device != src.device:
-            raise ValueError("softmax_topk: bias must be [K] on the source's device")
-    k = int(k)
+    src, ksplit, M, K, k = _head_source("softmax_topk", "M", logits, slabs, bias, k)
     idx = torch.empty((M, k), device=src.device, dtype=torch.int32)
     prob = torch.empty((M, k), device=src.device, dtype=torch.float32)
     z = None
@@ -387,10 +396,6 @@ def softmax_topk(logits: torch.Tensor | None = None, k: int = 5, *, slabs: torch
         else:
             nat.call("anx_cpu_softmax_topk", *args)
     return (idx, prob, z) if return_logits else (idx, prob)
-
-
-MAX_VIEWS = 32           # kMaxViews (anx/ops.hpp)
-_VIEWS_MAX_K = 7680      # kSoftmaxViewsMaxK: two rows of the view-averaging head in LDS on the GPU
 
 
 def softmax_topk_views(logits: torch.Tensor | None = None, views: int | None = None, k: int = 5, *,
@@ -408,33 +413,14 @@ def softmax_topk_views(logits: torch.Tensor | None = None, views: int | None = N
     :func:`softmax_topk` still orders them by their logits. The host function ``cpu::softmax_topk_views`` (CPU
     tensors) is the definition; ``expf`` differs between host and device, so both are held to an fp64 softmax mean
     rather than to each other's bits."""
-    if (logits is None) == (slabs is None):
-        raise ValueError("softmax_topk_views: give logits [N*V,K] or slabs [ksplit,N*V,K], not both")
     if not isinstance(views, int) or isinstance(views, bool) or not 1 <= views <= MAX_VIEWS:
         raise ValueError(f"softmax_topk_views: views must be an integer 1 .. {MAX_VIEWS}, got {views!r}")
-    src = logits if slabs is None else slabs
-    _check(src, "softmax_topk_views")
-    if slabs is None:
-        if src.dim() != 2:
-            raise ValueError("softmax_topk_views: logits must be [N*V,K]")
-        if bias is not None:
-            raise ValueError("softmax_topk_views: a bias goes with slabs")
-        ksplit, (M, K) = 1, src.shape
-    else:
-        if src.dim() != 3 or src.shape[0] < 1:
-            raise ValueError("softmax_topk_views: slabs must be [ksplit,N*V,K] with ksplit >= 1")
-        ksplit, M, K = src.shape
+    src, ksplit, M, K, k = _head_source("softmax_topk_views", "N*V", logits, slabs, bias, k)
     if M % views:
         raise ValueError(f"softmax_topk_views: {M} rows are no whole number of images of {views} views")
-    if K < 1 or not 1 <= int(k) <= min(K, MAX_TOPK):
-        raise ValueError(f"softmax_topk_views: need 1 <= k <= min(K, {MAX_TOPK}), got k = {k} for K = {K}")
-    if src.is_cuda and K > _VIEWS_MAX_K:
-        raise ValueError(f"softmax_topk_views: at most {_VIEWS_MAX_K} classes on the GPU, got {K}")
-    if bias is not None:
-        _check(bias, "softmax_topk_views bias")
-        if tuple(bias.shape) != (K,) or bias.device != src.device:
-            raise ValueError("softmax_topk_views: bias must be [K] on the source's device")
-    k, N = int(k), M // views
+    if src.is_cuda and K > VIEWS_MAX_CLASSES:
+        raise ValueError(f"softmax_topk_views: at most {VIEWS_MAX_CLASSES} classes on the GPU, got {K}")
+    N = M // views
     idx = torch.empty((N, k), device=src.device, dtype=torch.int32)
     prob = torch.empty((N, k), device=src.device, dtype=torch.float32)
     probs = torch.empty((N, K), device=src.device, dtype=torch.float32) if return_probs else None

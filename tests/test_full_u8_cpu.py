@@ -7,7 +7,7 @@ import pytest
 from anx import _native as nat
 from anx.utils.tuning import KNOBS, default_knob, knob_value
 
-NEW = ("anx_full_forward_u8", "anx_full_forward_mark_u8", "anx_full_set_input_norm", "anx_full_last_input")
+NEW = ("anx_full_run", "anx_full_set_input_norm", "anx_full_last_input")
 
 
 def test_symbols_exported_and_declared():
@@ -37,11 +37,30 @@ def test_null_engine_is_an_error_with_a_message():
     three = (C.c_float * 3)(1.0, 1.0, 1.0)
     for name, args in (("anx_full_last_input", (None, buf, len(buf))),
                        ("anx_full_set_input_norm", (None, three, three)),
-                       ("anx_full_forward_u8", (None, None, 1, None, None)),
-                       ("anx_full_forward_mark_u8", (None, None, 1, None, None))):
+                       ("anx_full_run", (None, C.byref(nat.FullCallC(rows=1)), None)),  # floats
+                       ("anx_full_run", (None, C.byref(nat.FullCallC(rows=1, u8=1)), None)),  # bytes
+                       ("anx_full_run", (None, C.byref(nat.FullCallC(rows=1, mark=1)), None)),
+                       ("anx_full_run", (None, C.byref(nat.FullCallC(rows=1, u8=1, mark=1)), None))):
         assert getattr(lib, name)(*args) != 0, name
         msg = nat.lib().anx_last_error().decode()
         assert name in msg and "no engine" in msg, (name, msg)
+
+
+def test_full_run_refuses_a_null_call_and_a_wrong_size():
+    """anx_full_run checks the call, then its size, then the engine: a null engine reaches "no engine" only with the
+    size the library accepts, which is therefore ctypes' sizeof(FullCallC)."""
+    lib, err = nat.bf16(), lambda: nat.lib().anx_last_error().decode()
+    for engine in (None, C.c_void_p()):  # the size is looked at before the engine: a null engine changes nothing
+        assert lib.anx_full_run(engine, None, None) != 0
+        assert err().startswith("anx_full_run: ")
+        short = nat.FullCallC(rows=1)
+        short.size = C.sizeof(nat.FullCallC) - 8
+        assert lib.anx_full_run(engine, C.byref(short), None) != 0
+        assert err().startswith("anx_full_run: ") and "size" in err(), err()
+    ok = nat.FullCallC(rows=1)
+    assert ok.size == C.sizeof(nat.FullCallC)
+    assert lib.anx_full_run(None, C.byref(ok), None) != 0
+    assert "no engine" in err() and "size" not in err(), err()
 
 
 # ---- the byte loader's address plan (conv1_bf16_ring.hip, "U8: the same plan in bytes"), mirrored from the kernel's

@@ -113,7 +113,7 @@ def test_abi_version_5():
 def test_symbols_exported_and_declared():
     for lib, sigs, names in ((nat.lib(), nat._SIGS, ("anx_softmax_topk", "anx_cpu_softmax_topk")),
                              (nat.bf16(), nat._BF16_SIGS,
-                              ("anx_full_classify", "anx_full_classify_u8", "anx_full_last_head"))):
+                              ("anx_full_run", "anx_full_last_head"))):
         for name in names:
             assert name in sigs, name
             fn = getattr(lib, name)  # AttributeError: the library does not export it
@@ -141,8 +141,8 @@ def test_rejected_arguments_name_the_function():
 def test_null_engine_is_an_error_with_a_message():
     lib = nat.bf16()
     buf = C.create_string_buffer(32)
-    for name, args in (("anx_full_classify", (None, None, 1, 5, None, None, None, None, 0)),
-                       ("anx_full_classify_u8", (None, None, 1, 5, None, None, None, None, 0)),
+    for name, args in (("anx_full_run", (None, C.byref(nat.FullCallC(rows=1, k=5)), None)),  # with head, floats
+                       ("anx_full_run", (None, C.byref(nat.FullCallC(rows=1, k=5, u8=1)), None)),  # with head, bytes
                        ("anx_full_last_head", (None, buf, len(buf)))):
         assert getattr(lib, name)(*args) != 0, name
         msg = nat.lib().anx_last_error().decode()

@@ -2,6 +2,8 @@
 anx.ops.softmax_topk_views on CPU tensors) against the fp64 mean of softmaxes (softmax_topk_views_cases.py has the
 bound), the slab route against the logits route bit for bit, one view against softmax_topk, the crafted rows, and the
 argument errors. The device tests (test_softmax_topk_views_gpu.py) hold the kernel to the same reference."""
+import ctypes as C
+
 import pytest
 import torch
 
@@ -125,7 +127,7 @@ def test_python_argument_checks():
 def test_abi_version_7_and_symbols():
     assert nat.lib().anx_abi_version() >= 7
     for lib, sigs, names in ((nat.lib(), nat._SIGS, ("anx_softmax_topk_views", "anx_cpu_softmax_topk_views")),
-                             (nat.bf16(), nat._BF16_SIGS, ("anx_full_classify_views", "anx_full_classify_views_u8"))):
+                             (nat.bf16(), nat._BF16_SIGS, ("anx_full_run",))):
         for name in names:
             fn = getattr(lib, name)  # AttributeError: the library does not export it
             assert fn.argtypes == sigs[name][1] and fn.restype is sigs[name][0]
@@ -154,7 +156,8 @@ def test_rejected_arguments_name_the_function():
 
 def test_null_engine_is_an_error_with_a_message():
     lib = nat.bf16()
-    for name in ("anx_full_classify_views", "anx_full_classify_views_u8"):
-        assert getattr(lib, name)(None, None, 10, 10, 5, None, None, None, None, 0) != 0, name
+    for u8 in (0, 1):  # with views, floats and bytes
+        call = nat.FullCallC(rows=10, views=10, k=5, u8=u8)
+        assert lib.anx_full_run(None, C.byref(call), None) != 0, u8
         msg = nat.lib().anx_last_error().decode()
-        assert name in msg and "no engine" in msg, (name, msg)
+        assert "anx_full_run" in msg and "no engine" in msg, (u8, msg)
