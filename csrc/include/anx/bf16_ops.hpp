@@ -160,6 +160,14 @@ struct FullPathRecord {
 //    rows = N * V images, image-major (row i * V + v is view v of image i), and idx / prob rank the mean of each
 //    image's V softmax rows (cpu::softmax_topk_views; by probability, so V = 1 is not views == 0). A launch chunk then
 //    holds whole images: the chunk step is the largest multiple of V the engine's chunk holds.
+//  * labels != null, the evaluation head in place of the classifier head (cpu::softmax_eval is the definition; a call
+//    has one head, so idx and prob stay null): labels int32 [N] on the device, one per image, k > 0 the top-k
+//    threshold, and at least one of rank int32 [N], nll fp32 [N], pred int32 [N], stats uint64 [kEvalStats] and
+//    confusion uint32 [classes][classes] on the device, each nullable. views as above (0: ranked by logit, and then
+//    classes <= kSoftmaxEvalMaxK). The head runs where the classifier head runs: on FC8's split-K slabs plus bias with
+//    Knobs::bf16_head, else on written logits; logits is nullable as for the classifier head. Launch chunks advance
+//    labels, rank, nll and pred by the chunk's images; stats and confusion are shared by all chunks (and by every
+//    lane that is handed the same ones): integer sums, so the totals do not depend on the order of arrival.
 //  * mark: record the engine's mark event on the stream once Conv2 + Pool2/LRN of the first chunk are enqueued (about
 //    half of the forward), for wait_mark.
 struct FullCall {
@@ -172,6 +180,12 @@ struct FullCall {
   int* idx = nullptr;
   float* prob = nullptr;
   int views = 0;
+  const int* labels = nullptr;
+  int* rank = nullptr;
+  float* nll = nullptr;
+  int* pred = nullptr;
+  uint64_t* stats = nullptr;
+  uint32_t* confusion = nullptr;
 };
 
 class FullEngine {
@@ -186,6 +200,10 @@ class FullEngine {
   // Null, or why run() refuses `c` (a static string): the one statement of the limits on k, views, rows and the
   // pointers (full_engine.cpp), which the C ABI reports word for word.
   const char* check(const FullCall& c) const;
+  // The part of check() that needs no engine: what the evaluation head's fields rule out among themselves (labels
+  // with idx / prob, outputs without labels, labels without k or without an output). Null for every call that names
+  // none of those fields, so for such calls check()'s reasons and their order are what they were.
+  static const char* check_eval(const FullCall& c);
   void set_input_norm(const float* scale, const float* offset);  // byte input: three values each
   // What the head of the last call read: "slabs" (it reduced FC8's split-K slabs), "logits" (written logits), null
   // when the last call had no head (k == 0). Recorded at the launch from host state.

@@ -136,6 +136,23 @@ int anx_softmax_topk_views(const float* src, int ksplit, size_t slab_stride, con
                            int k, int* idx, float* prob, float* probs_out, float* logits_out, void* stream);
 int anx_cpu_softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K,
                                int k, int* idx, float* prob, float* probs_out, float* logits_out);
+/* The evaluation head: the rows of anx_softmax_topk_views held to labels [N] (int32). V = 0: one row per image, the
+   score row is z (ranked by logit, anx_softmax_topk's rule); V in 1 .. 32: V rows per image, the score row is pbar
+   (anx_softmax_topk_views' rule). Per image with label y: pred = the class that ranks first, rank = the number of
+   classes that rank before y (rank < k exactly when y is among the k classes the head above returns), nll =
+   logf(S) - (z[y] - max) with S = sum expf(z - max) for V = 0, -logf(pbar[y]) with views. A label outside 0 .. K-1
+   marks an ignored image: rank -1, nll 0, pred written, nothing counted. Every other image adds into the
+   caller-zeroed stats (uint64 [4]: images, rank == 0, rank < k, and the loss in fixed point, q(nll) =
+   (uint64)((double)min(nll, 1024) * 2^32 + 0.5), a NaN or anything not < 1024 as 1024, below 0 as 0; mean loss =
+   stats[3] / 2^32 / stats[0]) and into confusion (uint32 [K][K]) at [y][pred]: integer sums, the same bits in any
+   order of arrival. rank, nll, pred, stats, confusion and logits_out ([N * max(V, 1)][K]) are each nullable.
+   1 <= k <= min(K, 16); on the device K <= 15360 with V = 0, K <= 7680 with views. */
+int anx_softmax_eval(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K, int k,
+                     const int* labels, int* rank, float* nll, int* pred, uint64_t* stats, uint32_t* confusion,
+                     float* logits_out, void* stream);
+int anx_cpu_softmax_eval(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K, int k,
+                         const int* labels, int* rank, float* nll, int* pred, uint64_t* stats, uint32_t* confusion,
+                         float* logits_out);
 /* conv2 input window geometry: pointer of (image n, pool1 row r), row stride and image stride (floats). */
 int anx_engine_window(void* e, const anx_tile_c* t, int n, int r, float** ptr, size_t* row_floats,
                       size_t* image_floats);
@@ -161,6 +178,12 @@ int anx_full_destroy(void* e);
    1 .. 32: x holds rows = N*V images, image-major, and the head is anx_softmax_topk_views (ranked by mean
    probability, so V = 1 is not views = 0); rows % V == 0, classes <= 7680, and a launch chunk holds whole images:
    an engine whose chunk is smaller than V refuses the call.
+   labels != null, the evaluation head in place of the classifier head (anx_softmax_eval; a call has one head, so idx
+   and prob must be null): labels [N] int32 on the device, one per image (not per row), k > 0 the top-k threshold, and
+   at least one of rank [N] int32, nll [N] fp32, pred [N] int32, stats (uint64 [4]) and confusion (uint32
+   [classes][classes]), each nullable, on the device. Launch chunks advance labels, rank, nll and pred by their images
+   and all add into the same stats and confusion. views as above; with views = 0, classes <= 15360. The five outputs
+   without labels are refused. These refusals need no engine and are made before it is looked at.
    mark: record the engine's mark event half-way (after Conv2 + Pool2/LRN of the first chunk); anx_full_wait_mark
    makes `stream` wait for the last recorded mark of engine e.
    A malformed call (null c, a wrong size, no engine, a missed limit) is refused with a message before anything is
@@ -176,6 +199,12 @@ typedef struct anx_full_call {
   int* idx;
   float* prob;
   int views;
+  const int* labels;
+  int* rank;
+  float* nll;
+  int* pred;
+  uint64_t* stats;
+  uint32_t* confusion;
 } anx_full_call;
 int anx_full_run(void* e, const anx_full_call* c, void* stream);
 int anx_full_wait_mark(void* e, void* stream);

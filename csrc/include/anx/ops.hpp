@@ -61,6 +61,35 @@ void softmax_topk(const float* src, int ksplit, size_t slab_stride, const float*
 constexpr int kMaxViews = 32;
 void softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K, int k,
                         int* idx, float* prob, float* probs_out, float* logits_out);
+// The evaluation head: the model held to labels. THE definition of hip::softmax_eval. The rows are those of
+// softmax_topk_views ([N * V][K], reduced from slabs (+ bias) in softmax_topk's order, into logits_out when given),
+// and V == 0 means one row per image (N rows). Per image i with label y = labels[i], the score row r is
+//   V == 0: z, the logits (softmax_topk's rule: ranked by logit);   V >= 1: pbar, softmax_topk_views' expressions,
+// ordered by value descending, then index ascending, a NaN as -inf (the rule of both heads above). Then
+//   pred[i] = the class that ranks first (idx[i][0] of the head above on the same rows);
+//   rank[i] = the number of classes that rank before y: rank < k exactly when y is among the k classes that head
+//             returns, and idx[i][rank[i]] == y there;
+//   nll[i]  = V == 0: logf(S) - (z[y] - m), m the row maximum and S = sum_c expf(z[c] - m) as softmax_topk sums it
+//             (finite where the probability underflows, +inf for a -inf label logit);
+//             V >= 1: -logf(pbar[y]), the log loss of the averaged prediction (+inf where pbar[y] is 0).
+// A label outside 0 .. K-1 (the -1 padding of a last batch) marks an ignored image: rank = -1, nll = 0, pred as
+// above, and nothing is counted. Every other image adds into the caller-zeroed counters
+//   stats[kEvalCount] += 1, stats[kEvalTop1] += rank == 0, stats[kEvalTopK] += rank < k,
+//   stats[kEvalNll] += eval_nll_q32(nll)      (fixed point, 32 fraction bits: mean loss = stats[3] / 2^32 / stats[0])
+//   confusion[y][pred] += 1                   (uint32 [K][K])
+// which are integer sums, so the totals are the same bits whatever order images, chunks, lanes and workgroups finish
+// in. rank, nll, pred, stats, confusion and logits_out are each nullable. 0 <= V <= kMaxViews, 1 <= k <= min(K,
+// kMaxTopK). nll of a row holding a NaN is unspecified, as prob is. The reference has no classifier head.
+enum { kEvalCount = 0, kEvalTop1 = 1, kEvalTopK = 2, kEvalNll = 3, kEvalStats = 4 };
+// q(x) = uint64(double(min(x, 1024)) 2^32 + 0.5): a NaN, or anything not < 1024 (+inf included), counts as 1024, and
+// a value below 0 (-logf of a mean that rounded a last bit above 1) as 0. At most 2^-33 off per image.
+__host__ __device__ inline uint64_t eval_nll_q32(float nll) {
+  const float c = !(nll < 1024.f) ? 1024.f : nll > 0.f ? nll : 0.f;
+  return static_cast<uint64_t>(static_cast<double>(c) * 4294967296.0 + 0.5);
+}
+void softmax_eval(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K, int k,
+                  const int* labels, int* rank, float* nll, int* pred, uint64_t* stats, uint32_t* confusion,
+                  float* logits_out);
 }  // namespace cpu
 
 // One source image of resize_crop_u8: H x W x 3 bytes, HWC, rows `pitch` bytes apart (pitch >= 3W), from any byte
@@ -278,6 +307,18 @@ hipError_t softmax_topk(const float* src, int ksplit, size_t slab_stride, const 
 constexpr int kSoftmaxViewsMaxK = 7680;
 hipError_t softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K,
                               int k, int* idx, float* prob, float* probs_out, float* logits_out, hipStream_t s);
+// The evaluation head (softmax_eval.hip; cpu::softmax_eval is the definition): one workgroup per image keeps the
+// score row in LDS (the logits with V == 0; a view's row and the running mean with views, as the view head does),
+// finds the first class in one argmax round and the label's rank in one counting pass, and thread 0 adds the image
+// into stats / confusion with integer atomics (no float atomics: the totals do not depend on arrival order). rank,
+// nll, pred, stats, confusion and logits_out are each nullable. The row(s) must fit the LDS: K <= kSoftmaxEvalMaxK
+// with V == 0 (no staging in logits_out as softmax_topk has it), K <= kSoftmaxViewsMaxK with views; that, V outside
+// 0 .. cpu::kMaxViews, k outside 1 .. min(K, kMaxTopK) and null src / labels return hipErrorInvalidValue before any
+// launch. N == 0 launches nothing. Same pred and the same order as the other two heads on the same rows' bits.
+constexpr int kSoftmaxEvalMaxK = kSoftmaxTopkLdsRow;
+hipError_t softmax_eval(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K, int k,
+                        const int* labels, int* rank, float* nll, int* pred, uint64_t* stats, uint32_t* confusion,
+                        float* logits_out, hipStream_t s);
 
 // The fused Winograd GEMM + output transform (wino_gemm.hip). V [P][points][C], U [points][K][C/groups]
 // (row = filter), bias + optional ReLU, NHWC store through `out` (Cb, c_off multiples of 4). P tiles of

@@ -113,7 +113,9 @@ const char* anx_last_error(void) { return g_err.c_str(); }
 // 8: one described call of the bf16 full model, anx_full_run(engine, anx_full_call*, stream). REMOVED: the eight
 //    entries it replaces, anx_full_forward, anx_full_forward_mark, anx_full_forward_u8, anx_full_forward_mark_u8,
 //    anx_full_classify, anx_full_classify_u8, anx_full_classify_views, anx_full_classify_views_u8
-int anx_abi_version(void) { return 8; }
+// 9: the evaluation head (anx_softmax_eval, anx_cpu_softmax_eval; anx_full_call grows by labels, rank, nll, pred,
+//    stats, confusion, so its size changes)
+int anx_abi_version(void) { return 9; }
 
 int anx_device_live(size_t out[4]) {
   if (!out) return fail("anx_device_live: no buffer");
@@ -345,6 +347,46 @@ int anx_cpu_softmax_topk_views(const float* src, int ksplit, size_t slab_stride,
     if (softmax_topk_args("anx_cpu_softmax_topk_views", src, ksplit, N, K, k, idx, prob)) return 1;
     if (V < 1 || V > anx::cpu::kMaxViews) return fail("anx_cpu_softmax_topk_views: 1 <= V <= 32 views");
     anx::cpu::softmax_topk_views(src, ksplit, slab_stride, bias, N, V, K, k, idx, prob, probs_out, logits_out);
+    return 0;
+  });
+}
+
+namespace {
+// the argument checks both softmax_eval entries share; 0 = fine
+int softmax_eval_args(const std::string& fn, const float* src, int ksplit, int N, int V, int K, int k, const int* labels) {
+  if (K < 1) return fail(fn + ": K >= 1 classes");
+  if (k < 1 || k > anx::cpu::kMaxTopK || k > K) return fail(fn + ": 1 <= k <= min(K, 16)");
+  if (ksplit < 1) return fail(fn + ": ksplit >= 1 slabs");
+  if (N < 0) return fail(fn + ": N >= 0 images");
+  if (V < 0 || V > anx::cpu::kMaxViews) return fail(fn + ": 0 <= V <= 32 views");
+  if (N > 0 && !src) return fail(fn + ": no source");
+  if (N > 0 && !labels) return fail(fn + ": no labels");
+  return 0;
+}
+}  // namespace
+
+int anx_softmax_eval(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K, int k,
+                     const int* labels, int* rank, float* nll, int* pred, uint64_t* stats, uint32_t* confusion,
+                     float* logits_out, void* stream) {
+  return guarded("anx_softmax_eval", [&] {
+    if (softmax_eval_args("anx_softmax_eval", src, ksplit, N, V, K, k, labels)) return 1;
+    const int most = V ? anx::hip::kSoftmaxViewsMaxK : anx::hip::kSoftmaxEvalMaxK;
+    if (K > most)
+      return fail("anx_softmax_eval: more than " + std::to_string(most) + " classes (" +
+                  (V ? "two rows" : "one row") + " must fit the LDS)");
+    return hip_status(anx::hip::softmax_eval(src, ksplit, slab_stride, bias, N, V, K, k, labels, rank, nll, pred, stats,
+                                             confusion, logits_out, S(stream)),
+                      "anx_softmax_eval");
+  });
+}
+
+int anx_cpu_softmax_eval(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K, int k,
+                         const int* labels, int* rank, float* nll, int* pred, uint64_t* stats, uint32_t* confusion,
+                         float* logits_out) {
+  return guarded("anx_cpu_softmax_eval", [&] {
+    if (softmax_eval_args("anx_cpu_softmax_eval", src, ksplit, N, V, K, k, labels)) return 1;
+    anx::cpu::softmax_eval(src, ksplit, slab_stride, bias, N, V, K, k, labels, rank, nll, pred, stats, confusion,
+                           logits_out);
     return 0;
   });
 }

@@ -49,9 +49,12 @@ int anx_full_run(void* e, const anx_full_call* c, void* stream) {
     if (c->size != sizeof(anx_full_call))
       return fail("anx_full_run: size is " + std::to_string(c->size) + ", sizeof(anx_full_call) is " +
                   std::to_string(sizeof(anx_full_call)));
+    const anx::FullCall call{c->x,    c->u8 != 0, c->rows,   c->logits, c->mark != 0, c->k,     c->idx,      c->prob,
+                             c->views, c->labels,  c->rank,   c->nll,    c->pred,      c->stats, c->confusion};
+    // what the evaluation head's fields rule out among themselves needs no engine
+    if (const char* why = anx::FullEngine::check_eval(call)) return fail(std::string("anx_full_run: ") + why);
     if (!e) return fail("anx_full_run: no engine");
     auto* eng = static_cast<anx::FullEngine*>(e);
-    const anx::FullCall call{c->x, c->u8 != 0, c->rows, c->logits, c->mark != 0, c->k, c->idx, c->prob, c->views};
     if (const char* why = eng->check(call)) return fail(std::string("anx_full_run: ") + why);
     return hip_status(eng->run(call, S(stream)), "anx_full_run");
   });

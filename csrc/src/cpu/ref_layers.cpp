@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "anx/ops.hpp"
+#include "pairwise_sum.hpp"
 
 namespace anx::cpu {
 
@@ -22,19 +23,6 @@ void decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, 
     c = c + 1 == C ? 0 : c + 1;
   }
 }
-
-namespace {
-// fp32 pairwise sum: the error grows with log2(n) roundings, not n
-float pairwise_sum(const float* v, size_t n) {
-  if (n <= 8) {
-    float s = 0.f;
-    for (size_t i = 0; i < n; ++i) s += v[i];
-    return s;
-  }
-  const size_t h = n / 2;
-  return pairwise_sum(v, h) + pairwise_sum(v + h, n - h);
-}
-}  // namespace
 
 void softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k, int* idx,
                   float* prob, float* logits_out) {

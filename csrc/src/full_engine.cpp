@@ -171,17 +171,32 @@ void FullEngine::set_input_norm(const float* scale, const float* offset) {
   for (int c = 0; c < 3; ++c) norm_.sc[c] = scale[c], norm_.of[c] = offset[c];
 }
 
+const char* FullEngine::check_eval(const FullCall& c) {
+  const bool outputs = c.rank || c.nll || c.pred || c.stats || c.confusion;
+  if (!c.labels) return outputs ? "rank, nll, pred, stats and confusion go with labels" : nullptr;
+  if (c.idx || c.prob) return "a call has one head: labels (the evaluation head) go without idx and prob";
+  if (c.k == 0) return "labels need the top-k threshold (k > 0)";
+  if (!outputs) return "no output (rank, nll, pred, stats, confusion)";
+  return nullptr;
+}
+
 const char* FullEngine::check(const FullCall& c) const {
-  static_assert(cpu::kMaxTopK == 16 && cpu::kMaxViews == 32 && hip::kSoftmaxViewsMaxK == 7680, "the reasons spell them");
+  static_assert(cpu::kMaxTopK == 16 && cpu::kMaxViews == 32 && hip::kSoftmaxViewsMaxK == 7680 &&
+                    hip::kSoftmaxEvalMaxK == 15360,
+                "the reasons spell them");
+  if (const char* why = check_eval(c)) return why;  // null for every call without the evaluation head's fields
   if (c.rows < 0) return "rows < 0";
   if (c.k < 0 || c.k > cpu::kMaxTopK || c.k > classes_) return "k outside 0 .. min(classes, 16)";
   if (c.k == 0 && (c.idx || c.prob || c.views != 0)) return "idx, prob and views go with a head (k > 0)";
   if (c.rows > 0 && !c.x) return "no input (x)";
-  if (c.rows > 0 && (c.k ? !c.idx || !c.prob : !c.logits)) return c.k ? "no output (idx, prob)" : "no output (logits)";
+  if (c.rows > 0 && !c.labels && (c.k ? !c.idx || !c.prob : !c.logits))
+    return c.k ? "no output (idx, prob)" : "no output (logits)";
   if (c.views < 0 || c.views > cpu::kMaxViews) return "views outside 0 .. 32";
   if (c.views && c.rows % c.views != 0) return "rows are no whole number of images of `views` views";
   if (c.views && chunk_ < c.views) return "the engine's launch chunk is smaller than one image's views";
   if (c.views && classes_ > hip::kSoftmaxViewsMaxK) return "the view-averaging head takes at most 7680 classes";
+  if (c.labels && !c.views && classes_ > hip::kSoftmaxEvalMaxK)
+    return "the evaluation head takes at most 15360 classes without views";
   return nullptr;
 }
 
@@ -189,7 +204,11 @@ hipError_t FullEngine::run_head(const FullCall& ch, const float* src, int ksplit
                                 hipStream_t s) {
   float* const z = ch.logits ? ch.logits : hlog_.get();  // where the chunk's logits are, or would be
   const bool slabs = src != z;                           // else they are written: nothing to write again
-  if (ch.views)
+  if (ch.labels)
+    ANX_TRY(hip::softmax_eval(src, ksplit, slab_stride, bias, ch.views ? ch.rows / ch.views : ch.rows, ch.views, classes_,
+                              ch.k, ch.labels, ch.rank, ch.nll, ch.pred, ch.stats, ch.confusion,
+                              slabs ? ch.logits : nullptr, s));
+  else if (ch.views)
     ANX_TRY(hip::softmax_topk_views(src, ksplit, slab_stride, bias, ch.rows / ch.views, ch.views, classes_, ch.k, ch.idx,
                                     ch.prob, nullptr, slabs ? ch.logits : nullptr, s));
   else  // a row too long for the kernel's LDS is staged in z (written logits are read back from there)
@@ -278,7 +297,13 @@ hipError_t FullEngine::run(const FullCall& c, hipStream_t s) {
     FullCall ch = c;
     ch.rows = n;
     if (c.logits) ch.logits = c.logits + static_cast<size_t>(n0) * classes_;
-    if (c.k) {
+    if (c.labels) {  // the per-image arrays by the chunk's images; stats and confusion are every chunk's
+      const size_t i0 = static_cast<size_t>(V ? n0 / V : n0);
+      ch.labels = c.labels + i0;
+      if (c.rank) ch.rank = c.rank + i0;
+      if (c.nll) ch.nll = c.nll + i0;
+      if (c.pred) ch.pred = c.pred + i0;
+    } else if (c.k) {
       const size_t o0 = static_cast<size_t>(V ? n0 / V : n0) * c.k;
       ch.idx = c.idx + o0;
       ch.prob = c.prob + o0;

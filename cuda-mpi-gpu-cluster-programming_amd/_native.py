@@ -48,9 +48,12 @@ class XferC(C.Structure):
 
 
 class FullCallC(C.Structure):
-    """anx_full_call: one call of the bf16 full model (``size`` is filled in; ``k`` 0 is the plain forward)."""
+    """anx_full_call: one call of the bf16 full model (``size`` is filled in; ``k`` 0 is the plain forward; ``labels``
+    selects the evaluation head, whose fields default to null)."""
     _fields_ = [("size", C.c_size_t), ("x", C.c_void_p), ("u8", C.c_int), ("rows", C.c_int), ("logits", C.c_void_p),
-                ("mark", C.c_int), ("k", C.c_int), ("idx", C.c_void_p), ("prob", C.c_void_p), ("views", C.c_int)]
+                ("mark", C.c_int), ("k", C.c_int), ("idx", C.c_void_p), ("prob", C.c_void_p), ("views", C.c_int),
+                ("labels", C.c_void_p), ("rank", C.c_void_p), ("nll", C.c_void_p), ("pred", C.c_void_p),
+                ("stats", C.c_void_p), ("confusion", C.c_void_p)]
 
     def __init__(self, **fields):
         super().__init__(size=C.sizeof(FullCallC), **fields)
@@ -100,6 +103,8 @@ _SIGS = {
     "anx_cpu_resize_crop_u8_flip": (_I, [_P, _P, _I, _P, _I, _I]),
     "anx_softmax_topk_views": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "anx_cpu_softmax_topk_views": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "anx_softmax_eval": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "anx_cpu_softmax_eval": (_I, [_P, _I, _SZ, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "anx_cpu_engine_set_input_norm": (_I, [_P, _P, _P]),
     "anx_cpu_engine_forward_u8": (_I, [_P, _P, _I, _P]),
     "anx_cpu_engine_tile_forward_u8": (_I, [_P, _P, _I, C.POINTER(TileC), _P]),

@@ -20,6 +20,10 @@ one :func:`anx.ops.resize_crop_u8` launch (antialiased resize + centre crop, int
 of the model, then the byte path above. ``classify_images(views="ten")`` is AlexNet's ten-view protocol (corner and
 centre crops and their mirror images, one resize launch for all of them) on ``classify(views=10)``, whose head
 kernel averages the views' softmax outputs on chip (:func:`anx.ops.softmax_topk_views`).
+
+:meth:`AlexNetFull.evaluate` / :meth:`AlexNetFull.evaluate_images` hold the model to labels on the chip
+(:func:`anx.ops.softmax_eval`): per image the rank of the true class, the loss and the prediction, and running device
+counters that :func:`anx.ops.eval_summary` turns into top-1 / top-k error and mean loss once the set is through.
 """
 from __future__ import annotations
 
@@ -71,6 +75,37 @@ class _Head(NamedTuple):
     idx: torch.Tensor
     prob: torch.Tensor
     views: int = 0
+
+    def part(self, lo: int, hi: int) -> "_Head":
+        """The head of images ``lo .. hi`` (a lane's share)."""
+        return self._replace(idx=self.idx[lo:hi], prob=self.prob[lo:hi])
+
+    def describe(self, call) -> None:
+        call.k, call.idx, call.prob, call.views = self.k, self.idx.data_ptr(), self.prob.data_ptr(), self.views
+
+
+class _EvalHead(NamedTuple):
+    """The evaluation head of a call: ``labels`` and the per-image outputs ``rank`` / ``nll`` / ``pred`` ``[N]``, the
+    running counters ``stats`` and ``confusion`` (either may be None), ``k`` the top-k threshold; ``views`` as in
+    :class:`_Head`."""
+    k: int
+    labels: torch.Tensor
+    rank: torch.Tensor
+    nll: torch.Tensor
+    pred: torch.Tensor
+    stats: torch.Tensor | None = None
+    confusion: torch.Tensor | None = None
+    views: int = 0
+
+    def part(self, lo: int, hi: int) -> "_EvalHead":
+        """The head of images ``lo .. hi`` (a lane's share): every lane adds into the same counters."""
+        return self._replace(labels=self.labels[lo:hi], rank=self.rank[lo:hi], nll=self.nll[lo:hi], pred=self.pred[lo:hi])
+
+    def describe(self, call) -> None:
+        call.k, call.views = self.k, self.views
+        call.labels, call.rank, call.nll, call.pred = (t.data_ptr() for t in (self.labels, self.rank, self.nll, self.pred))
+        call.stats = self.stats.data_ptr() if self.stats is not None else None
+        call.confusion = self.confusion.data_ptr() if self.confusion is not None else None
 
 
 class AlexNetFull:
@@ -213,12 +248,12 @@ class AlexNetFull:
 
     def _launch(self, x, z, head, stream, mark: bool) -> None:
         """This engine's one native call on images ``x`` (the only place that names the entry point): the forward
-        into logits ``z``, or with a :class:`_Head` the classify call (``z`` may be None). ``stream`` None: the current
-        stream. ``mark``: record the mid-forward mark that ``anx_full_wait_mark`` waits for."""
+        into logits ``z``, or with a :class:`_Head` / :class:`_EvalHead` the call with that head (``z`` may be None).
+        ``stream`` None: the current stream. ``mark``: record the mid-forward mark that ``anx_full_wait_mark`` waits for."""
         call = nat.FullCallC(x=x.data_ptr(), u8=int(x.dtype == torch.uint8), rows=x.shape[0],
                              logits=z.data_ptr() if z is not None else None, mark=int(mark))
         if head is not None:
-            call.k, call.idx, call.prob, call.views = head.k, head.idx.data_ptr(), head.prob.data_ptr(), head.views
+            head.describe(call)
         nat.call("anx_full_run", self._h, C.byref(call), stream if stream is not None else nat.stream_ptr(self.device))
 
     def _run(self, x, z, head, free: bool = False, pre_lane=None, on_lane=None) -> None:
@@ -232,7 +267,7 @@ class AlexNetFull:
             eng = self._lane(i)
             eng._ensure((hi - lo) * V)
             eng._launch(x[lo * V:hi * V], z[lo * V:hi * V] if z is not None else None,
-                        head._replace(idx=head.idx[lo:hi], prob=head.prob[lo:hi]) if head is not None else None,
+                        head.part(lo, hi) if head is not None else None,
                         st.cuda_stream if st is not None else None, lead)
             if lead:
                 return lambda s: nat.call("anx_full_wait_mark", eng._h, s.cuda_stream)
@@ -364,6 +399,60 @@ class AlexNetFull:
         head = self._check_head(x, k, idx_out, prob_out, self._check_views(x, views))
         self._run(x, None, head, True, pre_lane, on_lane)
         return head.idx, head.prob
+
+    def _check_eval(self, x, labels, k, views, stats, confusion, out) -> _EvalHead:
+        """evaluate's head: ``k`` and ``views`` checked as classify checks them, ``labels``, ``stats``, ``confusion``
+        and ``out`` validated like ``out`` in :meth:`_check` (dtype, shape, contiguity, device), the per-image outputs
+        allocated when not given."""
+        from ..ops import EVAL_MAX_CLASSES, MAX_TOPK, _eval_outputs
+        self._check_x(x)
+        views = self._check_views(x, views)
+        kmax = min(self.classes, MAX_TOPK)
+        if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= kmax:
+            raise ValueError(f"k must be an integer with 1 <= k <= min(classes, {MAX_TOPK}) = {kmax}, got {k!r}")
+        if not views and self.classes > EVAL_MAX_CLASSES:
+            raise ValueError(f"the evaluation head takes at most {EVAL_MAX_CLASSES} classes without views")
+        N = x.shape[0] // (views or 1)
+        rank, nll, pred = _eval_outputs("evaluate", N, self.classes, self.device, labels, stats, confusion, out)
+        return _EvalHead(k, labels, rank, nll, pred, stats, confusion, views)
+
+    def evaluate(self, x: torch.Tensor, labels: torch.Tensor, k: int = 5, *, views: int | None = None,
+                 stats: torch.Tensor | None = None, confusion: torch.Tensor | None = None, out=None):
+        """x as in :meth:`forward`, held to ``labels`` (``int32 [N]`` on the model's device; with ``views`` one per
+        image, not per row) -> ``(rank [N] int32, nll [N] fp32, pred [N] int32)``: the number of classes that rank
+        before the true one, the negative log-likelihood and the top-1 prediction, equal bit for bit to
+        ``anx.ops.softmax_eval(forward(x), labels, k, views=views)`` (which has the definitions). The evaluation head
+        kernel runs where :meth:`classify`'s runs (on FC8's split-K slabs with knob ``bf16_head``; :meth:`last_head`
+        tells), so the logits never reach device memory.
+
+        ``stats`` (``int64 [4]``, zeroed once by the caller) and ``confusion`` (``int32 [classes, classes]``) are
+        running device counters that every call adds into: images, top-1 hits, top-``k`` hits, the loss in fixed
+        point, and ``[label, pred]`` counts. A label outside ``0 .. classes-1`` (``-1`` padding) leaves them alone.
+        They are integer sums: lanes, launch chunks and workgroups may finish in any order and the totals are the
+        same bits. Nothing here synchronises: run the whole validation set, then read
+        ``anx.ops.eval_summary(stats, k)``. ``views`` and lanes as in :meth:`classify`; every lane adds into the
+        same ``stats`` and ``confusion``. ``out``: ``(rank, nll, pred)`` tensors to write into."""
+        head = self._check_eval(x, labels, k, views, stats, confusion, out)
+        self._run(x, None, head)
+        return head.rank, head.nll, head.pred
+
+    def evaluate_async(self, x: torch.Tensor, labels: torch.Tensor, k: int = 5, *, views: int | None = None,
+                       stats: torch.Tensor | None = None, confusion: torch.Tensor | None = None, out=None,
+                       on_lane=None, pre_lane=None):
+        """:meth:`evaluate` in the throughput form of :meth:`forward_async` (free-running lanes on their own streams,
+        never joined per call). :meth:`join` before reading the outputs, ``stats`` or ``confusion``."""
+        head = self._check_eval(x, labels, k, views, stats, confusion, out)
+        self._run(x, None, head, True, pre_lane, on_lane)
+        return head.rank, head.nll, head.pred
+
+    def evaluate_images(self, images, labels: torch.Tensor, k: int = 5, resize: int | None = 256, views=None, *,
+                        stats: torch.Tensor | None = None, confusion: torch.Tensor | None = None, out=None):
+        """:meth:`evaluate` of byte images of any size (``images``, ``resize`` and the workspace as in
+        :meth:`forward_images`). ``views="ten"`` is AlexNet's evaluation protocol end to end: the ten crops of
+        :meth:`classify_images`, the forward, and top-1 / top-``k`` hits and the log loss of the averaged
+        prediction, counted on the device."""
+        return self.evaluate(self._preprocess(images, resize, views), labels, k, views=10 if views == "ten" else None,
+                             stats=stats, confusion=confusion, out=out)
 
     def last_head(self, lane: int = 0) -> str | None:
         """What the head of the last call of this model's engine (``lane`` > 0: that side lane's) read: ``"slabs"``

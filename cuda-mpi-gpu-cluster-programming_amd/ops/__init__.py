@@ -34,7 +34,7 @@ from .. import _native as nat
 from ..config import conv_out_dim, pool_out_dim
 
 __all__ = ["conv2d", "relu", "maxpool", "lrn", "maxpool_lrn", "decode_u8", "softmax_topk", "resize_crop_u8",
-           "center_box", "ten_crop_boxes", "softmax_topk_views", "clear_cache"]
+           "center_box", "ten_crop_boxes", "softmax_topk_views", "softmax_eval", "eval_summary", "clear_cache"]
 
 _LRN_MODES = {"div_n": 0, "raw": 1}
 _pack_cache: dict = {}
@@ -433,6 +433,113 @@ def softmax_topk_views(logits: torch.Tensor | None = None, views: int | None = N
         else:
             nat.call("anx_cpu_softmax_topk_views", *args)
     return (idx, prob, probs) if return_probs else (idx, prob)
+
+
+EVAL_MAX_CLASSES = _HEAD_LDS_ROW  # kSoftmaxEvalMaxK: one row of the evaluation head in LDS on the GPU (views=None)
+EVAL_STATS = 4               # kEvalStats: images, top-1 hits, top-k hits, loss in 2^-32 units
+EVAL_NLL_CAP = 1024.0        # eval_nll_q32: a loss that is NaN or not below this counts as this
+
+
+def _eval_buffer(fn: str, name: str, t, shape, dtype, device, fill=None) -> torch.Tensor:
+    """An output of the evaluation head, checked as the kernels assume it (shape, dtype, contiguity, device), or made
+    when not given (``fill`` None: uninitialised)."""
+    if t is None:
+        return (torch.empty(shape, device=device, dtype=dtype) if fill is None
+                else torch.full(shape, fill, device=device, dtype=dtype))
+    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous()
+            or t.device != device):
+        got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else repr(t)
+        raise ValueError(f"{fn}: {name} must be a contiguous {dtype} {tuple(shape)} tensor on {device}, got {got}")
+    return t
+
+
+def _eval_outputs(fn: str, N: int, K: int, device, labels, stats, confusion, out):
+    """``labels``, ``stats``, ``confusion`` and ``out`` of the evaluation head, validated; returns ``(rank, nll,
+    pred)`` (allocated when ``out`` is None)."""
+    if labels is None:
+        raise ValueError(f"{fn}: labels (int32 [{N}], one per image) are required")
+    _eval_buffer(fn, "labels", labels, (N,), torch.int32, device)
+    if stats is not None:
+        _eval_buffer(fn, "stats", stats, (EVAL_STATS,), torch.int64, device)
+    if confusion is not None:
+        _eval_buffer(fn, "confusion", confusion, (K, K), torch.int32, device)
+    out = tuple(out) if out is not None else (None, None, None)
+    if len(out) != 3:
+        raise ValueError(f"{fn}: out must be (rank, nll, pred)")
+    return tuple(_eval_buffer(fn, name, t, (N,), dt, device)
+                 for t, dt, name in zip(out, (torch.int32, torch.float32, torch.int32), ("rank", "nll", "pred")))
+
+
+def _eval_views(fn: str, views) -> int:
+    if views is None:
+        return 0
+    if not isinstance(views, int) or isinstance(views, bool) or not 1 <= views <= MAX_VIEWS:
+        raise ValueError(f"{fn}: views must be None or an integer 1 .. {MAX_VIEWS}, got {views!r}")
+    return views
+
+
+def softmax_eval(logits: torch.Tensor | None = None, labels: torch.Tensor | None = None, k: int = 5, *,
+                 views: int | None = None, slabs: torch.Tensor | None = None, bias: torch.Tensor | None = None,
+                 stats: torch.Tensor | None = None, confusion: torch.Tensor | None = None, out=None,
+                 return_logits: bool = False):
+    """The evaluation head: the rows held to ``labels`` (``int32 [N]``, one per image, on the rows' device), one native
+    kernel. Returns ``(rank int32 [N], nll float32 [N], pred int32 [N])``, plus the reduced logits with
+    ``return_logits``.
+
+    The rows are ``logits`` or ``slabs`` (+ ``bias``) exactly as :func:`softmax_topk` takes them. ``views=None``: one
+    row per image, the score row is the logits (:func:`softmax_topk`'s order). ``views=V`` (1 to 32): ``V``
+    consecutive rows per image, the score row is the mean ``pbar`` of the views' softmax rows
+    (:func:`softmax_topk_views`' expressions and order). Per image with label ``y``:
+
+    * ``pred`` is the class that ranks first (value descending, then index ascending, a NaN as ``-inf``);
+    * ``rank`` is the number of classes that rank before ``y``: ``rank < k`` exactly when ``y`` is among the ``k``
+      classes the head of the same rows returns, and ``indices[i, rank[i]] == y`` there;
+    * ``nll`` is ``logf(S) - (z[y] - max)`` with ``S = sum(expf(z - max))`` without views (finite where the
+      probability underflows, ``+inf`` for a ``-inf`` label logit), and ``-logf(pbar[y])`` with views.
+
+    A label outside ``0 .. K-1`` (the ``-1`` padding of a last batch) marks an ignored image: ``rank = -1``,
+    ``nll = 0``, ``pred`` still written, nothing counted. Every other image adds into ``stats`` (``int64 [4]``, zeroed
+    by the caller once, accumulated into: images, ``rank == 0``, ``rank < k``, and the loss in units of ``2^-32``, a
+    NaN or anything not below 1024 counting as 1024; :func:`eval_summary` reads it) and into ``confusion`` (``int32
+    [K,K]``, ``[y, pred] += 1``). These are integer sums, so the totals are the same bits whatever order images,
+    streams and workgroups finish in. ``out``: ``(rank, nll, pred)`` tensors to write into. ``1 <= k <= min(K, 16)``;
+    on the GPU ``K <= 15360`` without views and ``K <= 7680`` with views. Nothing here synchronises. The host function
+    ``cpu::softmax_eval`` (CPU tensors) is the definition the GPU kernel is tested against."""
+    fn = "softmax_eval"
+    V = _eval_views(fn, views)
+    src, ksplit, M, K, k = _head_source(fn, "N*V" if V else "N", logits, slabs, bias, k)
+    if V and M % V:
+        raise ValueError(f"{fn}: {M} rows are no whole number of images of {V} views")
+    most = VIEWS_MAX_CLASSES if V else EVAL_MAX_CLASSES
+    if src.is_cuda and K > most:
+        raise ValueError(f"{fn}: at most {most} classes on the GPU {'with' if V else 'without'} views, got {K}")
+    N = M // V if V else M
+    rank, nll, pred = _eval_outputs(fn, N, K, src.device, labels, stats, confusion, out)
+    z = torch.empty((M, K), device=src.device, dtype=torch.float32) if return_logits else None
+    if N:
+        args = (src.data_ptr(), ksplit, M * K, bias.data_ptr() if bias is not None else None, N, V, K, k,
+                labels.data_ptr(), rank.data_ptr(), nll.data_ptr(), pred.data_ptr(),
+                stats.data_ptr() if stats is not None else None,
+                confusion.data_ptr() if confusion is not None else None, z.data_ptr() if z is not None else None)
+        if src.is_cuda:
+            with torch.cuda.device(src.device):
+                nat.call("anx_softmax_eval", *args, nat.stream_ptr(src.device))
+        else:
+            nat.call("anx_cpu_softmax_eval", *args)
+    return (rank, nll, pred, z) if return_logits else (rank, nll, pred)
+
+
+def eval_summary(stats: torch.Tensor, k: int) -> dict:
+    """The counters of :func:`softmax_eval` / ``AlexNetFull.evaluate`` as numbers: ``{"count", "top1_error",
+    "topk_error", "loss", "k"}`` (the errors and the mean loss are NaN while nothing is counted). Copying the four
+    counters to the host is the one place of an evaluation that waits for the device."""
+    if not isinstance(stats, torch.Tensor) or tuple(stats.shape) != (EVAL_STATS,) or stats.dtype != torch.int64:
+        raise ValueError(f"eval_summary: stats must be the int64 [{EVAL_STATS}] tensor of softmax_eval")
+    count, top1, topk, nll_q32 = (int(v) & (2 ** 64 - 1) for v in stats.tolist())  # the kernel's counters are unsigned
+    nan = float("nan")
+    return {"count": count, "top1_error": 1.0 - top1 / count if count else nan,
+            "topk_error": 1.0 - topk / count if count else nan,
+            "loss": nll_q32 / 2.0 ** 32 / count if count else nan, "k": int(k)}
 
 
 def relu(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
