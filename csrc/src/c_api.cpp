@@ -293,15 +293,17 @@ int anx_cpu_decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* 
 }
 
 namespace {
-// the argument checks both softmax_topk entries share; 0 = fine
-int softmax_topk_args(const std::string& fn, const float* src, int ksplit, int M, int K, int k, const int* idx,
-                      const float* prob) {
+// The argument checks the six softmax head entries share, in the order they always ran; 0 = fine. A top-k entry
+// passes no V (the views entries check their own 1 <= V afterwards) and `out` = idx && prob; an evaluation entry
+// passes its V, where 0 means no views, and `out` = labels.
+int softmax_head_args(const std::string& fn, const float* src, int ksplit, int n, int K, int k, const int* V, bool out) {
   if (K < 1) return fail(fn + ": K >= 1 classes");
   if (k < 1 || k > anx::cpu::kMaxTopK || k > K) return fail(fn + ": 1 <= k <= min(K, 16)");
   if (ksplit < 1) return fail(fn + ": ksplit >= 1 slabs");
-  if (M < 0) return fail(fn + ": M >= 0 rows");
-  if (M > 0 && !src) return fail(fn + ": no source");
-  if (M > 0 && (!idx || !prob)) return fail(fn + ": no output buffer (idx, prob)");
+  if (n < 0) return fail(fn + (V ? ": N >= 0 images" : ": M >= 0 rows"));
+  if (V && (*V < 0 || *V > anx::cpu::kMaxViews)) return fail(fn + ": 0 <= V <= 32 views");
+  if (n > 0 && !src) return fail(fn + ": no source");
+  if (n > 0 && !out) return fail(fn + (V ? ": no labels" : ": no output buffer (idx, prob)"));
   return 0;
 }
 }  // namespace
@@ -309,7 +311,7 @@ int softmax_topk_args(const std::string& fn, const float* src, int ksplit, int M
 int anx_softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k,
                      int* idx, float* prob, float* logits_out, void* stream) {
   return guarded("anx_softmax_topk", [&] {
-    if (softmax_topk_args("anx_softmax_topk", src, ksplit, M, K, k, idx, prob)) return 1;
+    if (softmax_head_args("anx_softmax_topk", src, ksplit, M, K, k, nullptr, idx && prob)) return 1;
     if (K > anx::hip::kSoftmaxTopkLdsRow && !logits_out)
       return fail("anx_softmax_topk: a row of more than " + std::to_string(anx::hip::kSoftmaxTopkLdsRow) +
                   " floats is staged in logits_out, which is null");
@@ -321,7 +323,7 @@ int anx_softmax_topk(const float* src, int ksplit, size_t slab_stride, const flo
 int anx_cpu_softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k,
                          int* idx, float* prob, float* logits_out) {
   return guarded("anx_cpu_softmax_topk", [&] {
-    if (softmax_topk_args("anx_cpu_softmax_topk", src, ksplit, M, K, k, idx, prob)) return 1;
+    if (softmax_head_args("anx_cpu_softmax_topk", src, ksplit, M, K, k, nullptr, idx && prob)) return 1;
     anx::cpu::softmax_topk(src, ksplit, slab_stride, bias, M, K, k, idx, prob, logits_out);
     return 0;
   });
@@ -330,7 +332,7 @@ int anx_cpu_softmax_topk(const float* src, int ksplit, size_t slab_stride, const
 int anx_softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K,
                            int k, int* idx, float* prob, float* probs_out, float* logits_out, void* stream) {
   return guarded("anx_softmax_topk_views", [&] {
-    if (softmax_topk_args("anx_softmax_topk_views", src, ksplit, N, K, k, idx, prob)) return 1;
+    if (softmax_head_args("anx_softmax_topk_views", src, ksplit, N, K, k, nullptr, idx && prob)) return 1;
     if (V < 1 || V > anx::cpu::kMaxViews) return fail("anx_softmax_topk_views: 1 <= V <= 32 views");
     if (K > anx::hip::kSoftmaxViewsMaxK)
       return fail("anx_softmax_topk_views: more than " + std::to_string(anx::hip::kSoftmaxViewsMaxK) +
@@ -344,32 +346,18 @@ int anx_softmax_topk_views(const float* src, int ksplit, size_t slab_stride, con
 int anx_cpu_softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K,
                                int k, int* idx, float* prob, float* probs_out, float* logits_out) {
   return guarded("anx_cpu_softmax_topk_views", [&] {
-    if (softmax_topk_args("anx_cpu_softmax_topk_views", src, ksplit, N, K, k, idx, prob)) return 1;
+    if (softmax_head_args("anx_cpu_softmax_topk_views", src, ksplit, N, K, k, nullptr, idx && prob)) return 1;
     if (V < 1 || V > anx::cpu::kMaxViews) return fail("anx_cpu_softmax_topk_views: 1 <= V <= 32 views");
     anx::cpu::softmax_topk_views(src, ksplit, slab_stride, bias, N, V, K, k, idx, prob, probs_out, logits_out);
     return 0;
   });
 }
 
-namespace {
-// the argument checks both softmax_eval entries share; 0 = fine
-int softmax_eval_args(const std::string& fn, const float* src, int ksplit, int N, int V, int K, int k, const int* labels) {
-  if (K < 1) return fail(fn + ": K >= 1 classes");
-  if (k < 1 || k > anx::cpu::kMaxTopK || k > K) return fail(fn + ": 1 <= k <= min(K, 16)");
-  if (ksplit < 1) return fail(fn + ": ksplit >= 1 slabs");
-  if (N < 0) return fail(fn + ": N >= 0 images");
-  if (V < 0 || V > anx::cpu::kMaxViews) return fail(fn + ": 0 <= V <= 32 views");
-  if (N > 0 && !src) return fail(fn + ": no source");
-  if (N > 0 && !labels) return fail(fn + ": no labels");
-  return 0;
-}
-}  // namespace
-
 int anx_softmax_eval(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K, int k,
                      const int* labels, int* rank, float* nll, int* pred, uint64_t* stats, uint32_t* confusion,
                      float* logits_out, void* stream) {
   return guarded("anx_softmax_eval", [&] {
-    if (softmax_eval_args("anx_softmax_eval", src, ksplit, N, V, K, k, labels)) return 1;
+    if (softmax_head_args("anx_softmax_eval", src, ksplit, N, K, k, &V, labels)) return 1;
     const int most = V ? anx::hip::kSoftmaxViewsMaxK : anx::hip::kSoftmaxEvalMaxK;
     if (K > most)
       return fail("anx_softmax_eval: more than " + std::to_string(most) + " classes (" +
@@ -384,7 +372,7 @@ int anx_cpu_softmax_eval(const float* src, int ksplit, size_t slab_stride, const
                          const int* labels, int* rank, float* nll, int* pred, uint64_t* stats, uint32_t* confusion,
                          float* logits_out) {
   return guarded("anx_cpu_softmax_eval", [&] {
-    if (softmax_eval_args("anx_cpu_softmax_eval", src, ksplit, N, V, K, k, labels)) return 1;
+    if (softmax_head_args("anx_cpu_softmax_eval", src, ksplit, N, K, k, &V, labels)) return 1;
     anx::cpu::softmax_eval(src, ksplit, slab_stride, bias, N, V, K, k, labels, rank, nll, pred, stats, confusion,
                            logits_out);
     return 0;

@@ -12,7 +12,6 @@
 #include <vector>
 
 #include "anx/ops.hpp"
-#include "pairwise_sum.hpp"
 
 namespace anx::cpu {
 
@@ -21,102 +20,6 @@ void decode_u8(const uint8_t* x, float* y, size_t n, int C, const float* scale, 
   for (size_t i = 0; i < n; ++i) {
     y[i] = std::fmaf(static_cast<float>(x[i]), scale[c], offset[c]);
     c = c + 1 == C ? 0 : c + 1;
-  }
-}
-
-void softmax_topk(const float* src, int ksplit, size_t slab_stride, const float* bias, int M, int K, int k, int* idx,
-                  float* prob, float* logits_out) {
-  const float inf = std::numeric_limits<float>::infinity();
-  std::vector<float> z(static_cast<size_t>(K)), e(static_cast<size_t>(K));
-  for (int m = 0; m < M; ++m) {
-    const float* x = src + static_cast<size_t>(m) * K;
-    for (int c = 0; c < K; ++c) {
-      float v;
-      int s = 0;
-      if (bias) {
-        v = bias[c];
-      } else {
-        v = x[c];
-        s = 1;
-      }
-      for (; s < ksplit; ++s) v = v + x[s * slab_stride + c];
-      z[c] = v;
-    }
-    if (logits_out) std::copy(z.begin(), z.end(), logits_out + static_cast<size_t>(m) * K);
-    float mx = -inf;
-    for (int c = 0; c < K; ++c)
-      if (z[c] > mx) mx = z[c];
-    for (int c = 0; c < K; ++c) e[c] = std::exp(z[c] - mx);
-    const float sum = pairwise_sum(e.data(), e.size());
-    // round j: the best element ranking strictly after round j-1's winner (value descending, index ascending;
-    // a NaN ranks with -inf, so the order is total)
-    float pv = inf;
-    int pi = -1;
-    for (int j = 0; j < k; ++j) {
-      float bv = -inf;
-      int bi = K;
-      for (int c = 0; c < K; ++c) {
-        const float v = z[c] != z[c] ? -inf : z[c];
-        if ((v < pv || (v == pv && c > pi)) && (bi == K || v > bv)) bv = v, bi = c;
-      }
-      pv = bv;
-      pi = bi;
-      idx[static_cast<size_t>(m) * k + j] = bi;
-      prob[static_cast<size_t>(m) * k + j] = std::exp(z[bi] - mx) / sum;
-    }
-  }
-}
-
-void softmax_topk_views(const float* src, int ksplit, size_t slab_stride, const float* bias, int N, int V, int K, int k,
-                        int* idx, float* prob, float* probs_out, float* logits_out) {
-  const float inf = std::numeric_limits<float>::infinity();
-  const size_t Kz = static_cast<size_t>(K);
-  std::vector<float> z(Kz), e(Kz), acc(Kz);
-  for (int i = 0; i < N; ++i) {
-    for (int v = 0; v < V; ++v) {
-      const size_t row = static_cast<size_t>(i) * V + v;
-      const float* x = src + row * Kz;
-      for (int c = 0; c < K; ++c) {  // softmax_topk's reduction, max, exponentials and sum
-        float a;
-        int s = 0;
-        if (bias) {
-          a = bias[c];
-        } else {
-          a = x[c];
-          s = 1;
-        }
-        for (; s < ksplit; ++s) a = a + x[s * slab_stride + c];
-        z[c] = a;
-      }
-      if (logits_out) std::copy(z.begin(), z.end(), logits_out + row * Kz);
-      float mx = -inf;
-      for (int c = 0; c < K; ++c)
-        if (z[c] > mx) mx = z[c];
-      for (int c = 0; c < K; ++c) e[c] = std::exp(z[c] - mx);
-      const float sum = pairwise_sum(e.data(), e.size());
-      for (int c = 0; c < K; ++c) {
-        const float p = e[c] / sum;
-        acc[c] = v ? acc[c] + p : p;
-      }
-    }
-    const float fv = static_cast<float>(V);
-    for (int c = 0; c < K; ++c) acc[c] = acc[c] / fv;
-    if (probs_out) std::copy(acc.begin(), acc.end(), probs_out + static_cast<size_t>(i) * Kz);
-    // softmax_topk's rounds, on the mean
-    float pv = inf;
-    int pi = -1;
-    for (int j = 0; j < k; ++j) {
-      float bv = -inf;
-      int bi = K;
-      for (int c = 0; c < K; ++c) {
-        const float val = acc[c] != acc[c] ? -inf : acc[c];
-        if ((val < pv || (val == pv && c > pi)) && (bi == K || val > bv)) bv = val, bi = c;
-      }
-      pv = bv;
-      pi = bi;
-      idx[static_cast<size_t>(i) * k + j] = bi;
-      prob[static_cast<size_t>(i) * k + j] = acc[bi];
-    }
   }
 }
 

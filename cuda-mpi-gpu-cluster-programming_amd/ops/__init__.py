@@ -344,10 +344,21 @@ VIEWS_MAX_CLASSES = 7680    # kSoftmaxViewsMaxK: two rows of the view-averaging 
 _HEAD_LDS_ROW = 15 * 1024   # kSoftmaxTopkLdsRow: a longer row is staged in the logits output on the GPU
 
 
+def _head_views(fn: str, views, none_ok: bool) -> int:
+    """``views`` of a head, checked: 1 .. 32, or None (returned as 0, the native side's "no views") where ``fn``
+    takes that."""
+    if views is None and none_ok:
+        return 0
+    if not isinstance(views, int) or isinstance(views, bool) or not 1 <= views <= MAX_VIEWS:
+        what = "None or an integer" if none_ok else "an integer"
+        raise ValueError(f"{fn}: views must be {what} 1 .. {MAX_VIEWS}, got {views!r}")
+    return views
+
+
 def _head_source(fn: str, rows: str, logits, slabs, bias, k):
-    """What both heads take: ``logits`` ``[rows,K]`` or ``slabs`` ``[ksplit,rows,K]`` (+ ``bias`` ``[K]``) and ``k``,
-    checked. Returns ``(src, ksplit, M, K, k)``; ``fn`` and ``rows`` (how ``fn`` names the row count) go into the
-    messages."""
+    """What every head takes: ``logits`` ``[rows,K]`` or ``slabs`` ``[ksplit,rows,K]`` (+ ``bias`` ``[K]``) and ``k``,
+    checked. Returns ``(src, head, M, K, k)``, ``head`` being the leading ``(src, ksplit, slab_stride, bias)``
+    arguments of the native entries; ``fn`` and ``rows`` (how ``fn`` names the row count) go into the messages."""
     if (logits is None) == (slabs is None):
         raise ValueError(f"{fn}: give logits [{rows},K] or slabs [ksplit,{rows},K], not both")
     src = logits if slabs is None else slabs
@@ -368,7 +379,7 @@ def _head_source(fn: str, rows: str, logits, slabs, bias, k):
         _check(bias, f"{fn} bias")
         if tuple(bias.shape) != (K,) or bias.device != src.device:
             raise ValueError(f"{fn}: bias must be [K] on the source's device")
-    return src, ksplit, M, K, int(k)
+    return src, (src.data_ptr(), ksplit, M * K, bias.data_ptr() if bias is not None else None), M, K, int(k)
 
 
 def softmax_topk(logits: torch.Tensor | None = None, k: int = 5, *, slabs: torch.Tensor | None = None,
@@ -382,15 +393,14 @@ def softmax_topk(logits: torch.Tensor | None = None, k: int = 5, *, slabs: torch
     ``-0.0`` and ``+0.0`` tie. ``p = exp(z - max) / sum(exp(z - max))`` in fp32. ``1 <= k <= min(K, 16)``. A row that
     holds a NaN or whose maximum is infinite still gets ``k`` distinct indices; its probabilities are unspecified.
     The host function ``cpu::softmax_topk`` (CPU tensors) is the definition the GPU kernel is tested against."""
-    src, ksplit, M, K, k = _head_source("softmax_topk", "M", logits, slabs, bias, k)
+    src, head, M, K, k = _head_source("softmax_topk", "M", logits, slabs, bias, k)
     idx = torch.empty((M, k), device=src.device, dtype=torch.int32)
     prob = torch.empty((M, k), device=src.device, dtype=torch.float32)
     z = None
     if return_logits or (src.is_cuda and K > _HEAD_LDS_ROW):
         z = torch.empty((M, K), device=src.device, dtype=torch.float32)
     if M:
-        args = (src.data_ptr(), ksplit, M * K, bias.data_ptr() if bias is not None else None, M, K, k, idx.data_ptr(),
-                prob.data_ptr(), z.data_ptr() if z is not None else None)
+        args = (*head, M, K, k, idx.data_ptr(), prob.data_ptr(), z.data_ptr() if z is not None else None)
         if src.is_cuda:
             nat.call("anx_softmax_topk", *args, nat.stream_ptr(src.device))
         else:
@@ -413,9 +423,8 @@ def softmax_topk_views(logits: torch.Tensor | None = None, views: int | None = N
     :func:`softmax_topk` still orders them by their logits. The host function ``cpu::softmax_topk_views`` (CPU
     tensors) is the definition; ``expf`` differs between host and device, so both are held to an fp64 softmax mean
     rather than to each other's bits."""
-    if not isinstance(views, int) or isinstance(views, bool) or not 1 <= views <= MAX_VIEWS:
-        raise ValueError(f"softmax_topk_views: views must be an integer 1 .. {MAX_VIEWS}, got {views!r}")
-    src, ksplit, M, K, k = _head_source("softmax_topk_views", "N*V", logits, slabs, bias, k)
+    views = _head_views("softmax_topk_views", views, none_ok=False)
+    src, head, M, K, k = _head_source("softmax_topk_views", "N*V", logits, slabs, bias, k)
     if M % views:
         raise ValueError(f"softmax_topk_views: {M} rows are no whole number of images of {views} views")
     if src.is_cuda and K > VIEWS_MAX_CLASSES:
@@ -425,8 +434,8 @@ def softmax_topk_views(logits: torch.Tensor | None = None, views: int | None = N
     prob = torch.empty((N, k), device=src.device, dtype=torch.float32)
     probs = torch.empty((N, K), device=src.device, dtype=torch.float32) if return_probs else None
     if N:
-        args = (src.data_ptr(), ksplit, M * K, bias.data_ptr() if bias is not None else None, N, views, K, k,
-                idx.data_ptr(), prob.data_ptr(), probs.data_ptr() if probs is not None else None, None)
+        args = (*head, N, views, K, k, idx.data_ptr(), prob.data_ptr(),
+                probs.data_ptr() if probs is not None else None, None)
         if src.is_cuda:
             with torch.cuda.device(src.device):
                 nat.call("anx_softmax_topk_views", *args, nat.stream_ptr(src.device))
@@ -470,14 +479,6 @@ def _eval_outputs(fn: str, N: int, K: int, device, labels, stats, confusion, out
                  for t, dt, name in zip(out, (torch.int32, torch.float32, torch.int32), ("rank", "nll", "pred")))
 
 
-def _eval_views(fn: str, views) -> int:
-    if views is None:
-        return 0
-    if not isinstance(views, int) or isinstance(views, bool) or not 1 <= views <= MAX_VIEWS:
-        raise ValueError(f"{fn}: views must be None or an integer 1 .. {MAX_VIEWS}, got {views!r}")
-    return views
-
-
 def softmax_eval(logits: torch.Tensor | None = None, labels: torch.Tensor | None = None, k: int = 5, *,
                  views: int | None = None, slabs: torch.Tensor | None = None, bias: torch.Tensor | None = None,
                  stats: torch.Tensor | None = None, confusion: torch.Tensor | None = None, out=None,
@@ -506,8 +507,8 @@ def softmax_eval(logits: torch.Tensor | None = None, labels: torch.Tensor | None
     on the GPU ``K <= 15360`` without views and ``K <= 7680`` with views. Nothing here synchronises. The host function
     ``cpu::softmax_eval`` (CPU tensors) is the definition the GPU kernel is tested against."""
     fn = "softmax_eval"
-    V = _eval_views(fn, views)
-    src, ksplit, M, K, k = _head_source(fn, "N*V" if V else "N", logits, slabs, bias, k)
+    V = _head_views(fn, views, none_ok=True)
+    src, head, M, K, k = _head_source(fn, "N*V" if V else "N", logits, slabs, bias, k)
     if V and M % V:
         raise ValueError(f"{fn}: {M} rows are no whole number of images of {V} views")
     most = VIEWS_MAX_CLASSES if V else EVAL_MAX_CLASSES
@@ -517,8 +518,7 @@ def softmax_eval(logits: torch.Tensor | None = None, labels: torch.Tensor | None
     rank, nll, pred = _eval_outputs(fn, N, K, src.device, labels, stats, confusion, out)
     z = torch.empty((M, K), device=src.device, dtype=torch.float32) if return_logits else None
     if N:
-        args = (src.data_ptr(), ksplit, M * K, bias.data_ptr() if bias is not None else None, N, V, K, k,
-                labels.data_ptr(), rank.data_ptr(), nll.data_ptr(), pred.data_ptr(),
+        args = (*head, N, V, K, k, labels.data_ptr(), rank.data_ptr(), nll.data_ptr(), pred.data_ptr(),
                 stats.data_ptr() if stats is not None else None,
                 confusion.data_ptr() if confusion is not None else None, z.data_ptr() if z is not None else None)
         if src.is_cuda:

@@ -166,3 +166,30 @@ def crafted_eval_rows(K: int):
     z = torch.stack([rows[name] for name, _ in picks])
     y = torch.tensor([c for _, c in picks], dtype=torch.int32)
     return z, y, [f"{name}@{c}" for name, c in picks]
+
+
+def special_value_rows(K: int):
+    """(z [R,K], y [R]): rows whose softmax is NaN or that hold nothing but ties, each with the labels 0, K // 2 and
+    K - 1: a lone +inf at an index > 0, all -inf, a NaN at index 0, all equal. No fp64 bound applies to them; what they
+    check is that the evaluation head's first round and count give the order of the other heads' rounds."""
+    g = torch.Generator().manual_seed(K)
+    lone_inf = torch.randn(K, generator=g)
+    lone_inf[K // 2] = float("inf")
+    nan_first = torch.randn(K, generator=g)
+    nan_first[0] = float("nan")
+    rows = [lone_inf, torch.full((K,), float("-inf")), nan_first, torch.full((K,), -2.5)]
+    labels = (0, K // 2, K - 1)
+    z = torch.stack([r for r in rows for _ in labels])
+    return z, torch.tensor([c for _ in rows for c in labels], dtype=torch.int32)
+
+
+def assert_rank_in_head(rank, pred, y, idx, what=""):
+    """pred is the head's first class, and rank the label's position in the head's indices idx [N,k] (with k == K every
+    label has one; a label the head did not return must rank at k or later)."""
+    rank, pred, y, idx = rank.cpu().tolist(), pred.cpu().tolist(), y.cpu().tolist(), idx.cpu().tolist()
+    for i, row in enumerate(idx):
+        assert pred[i] == row[0], f"{what}: image {i}: pred {pred[i]} is not the head's first class {row[0]}"
+        if y[i] in row:
+            assert rank[i] == row.index(y[i]), f"{what}: image {i}: rank {rank[i]}, the head has the label at {row.index(y[i])}"
+        else:
+            assert rank[i] >= len(row), f"{what}: image {i}: rank {rank[i]} < {len(row)}, but the head did not return the label"

@@ -9,8 +9,8 @@ import torch
 
 from anx import _native as nat
 from anx.ops import eval_summary, softmax_eval, softmax_topk, softmax_topk_views
-from softmax_eval_cases import (INT_MIN, assert_eval, crafted_eval_rows, expected_confusion, expected_stats, labels_for,
-                                nll_q32)
+from softmax_eval_cases import (INT_MIN, assert_eval, assert_rank_in_head, crafted_eval_rows, expected_confusion,
+                                expected_stats, labels_for, nll_q32, special_value_rows)
 from softmax_topk_cases import K_SIZES, random_rows
 
 V_SIZES = (None, 1, 2, 10, 32)
@@ -43,7 +43,7 @@ def test_random_rows_against_fp64(K, V):
 
 
 @pytest.mark.parametrize("V", (None, 1, 3), ids=lambda v: f"V{v}")
-@pytest.mark.parametrize("K", (1, 2, 65, 257, 1000))
+@pytest.mark.parametrize("K", (1, 2, 5, 65, 257, 1000))
 def test_crafted_rows(K, V):
     z1, y, names = crafted_eval_rows(K)
     v = V or 0
@@ -60,6 +60,13 @@ def test_crafted_rows(K, V):
             assert [int(rank[at[f"signed_zeros@{c}"]]) for c in (0, 1, 2)] == [0, 1, 2]
             assert not torch.isfinite(nll[at["minus_inf_entries@1"]]) and nll[at["minus_inf_entries@1"]] > 0
             assert torch.isfinite(nll[at["minus_inf_entries@0"]])  # -1e30: far down, but finite
+    z1, y = special_value_rows(K)  # the first round on +inf, -inf, NaN and ties: the other heads' order
+    z = z1.repeat_interleave(max(v, 1), dim=0)
+    rank, _, pred = softmax_eval(z, y, 1, views=V)
+    idx = softmax_topk(z, min(K, 16))[0] if V is None else softmax_topk_views(z, V, min(K, 16))[0]
+    assert_rank_in_head(rank, pred, y, idx, f"special values K={K} V={V}")
+    if V is None:  # by logit: the lone +inf at K // 2 wins, a row of -inf goes by index
+        assert pred.tolist()[:6] == [K // 2] * 3 + [0] * 3
 
 
 @pytest.mark.parametrize("V", (None, 2), ids=lambda v: f"V{v}")

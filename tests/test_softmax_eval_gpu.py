@@ -7,7 +7,8 @@ import torch
 
 from anx import _native as nat
 from anx.ops import softmax_eval, softmax_topk, softmax_topk_views
-from softmax_eval_cases import assert_eval, crafted_eval_rows, expected_confusion, expected_stats, labels_for
+from softmax_eval_cases import (assert_eval, assert_rank_in_head, crafted_eval_rows, expected_confusion, expected_stats,
+                                labels_for, special_value_rows)
 from softmax_topk_cases import random_rows
 
 pytestmark = pytest.mark.gpu
@@ -74,6 +75,12 @@ def test_crafted_rows(cuda, K, V):
     idx, probs = head_of(zd, V, min(K, 16))
     assert_eval(rank, nll, pred, z, y, v, probs, f"crafted K={K} V={V}")
     check_against_heads(rank, pred, y, idx, 1, f"crafted K={K} V={V}")
+    z1, y = special_value_rows(K)  # the first round on +inf, -inf, NaN and ties: the other heads' order, bit for bit
+    zd, yd = z1.repeat_interleave(max(v, 1), dim=0).to(cuda), y.to(cuda)
+    rank, _, pred = softmax_eval(zd, yd, 1, views=V)
+    assert_rank_in_head(rank, pred, y, head_of(zd, V, min(K, 16))[0], f"special values K={K} V={V}")
+    if V is None:  # by logit: the lone +inf at K // 2 wins, a row of -inf goes by index
+        assert pred.tolist()[:6] == [K // 2] * 3 + [0] * 3
 
 
 @pytest.mark.parametrize("K,V", [(1000, None), (7680, None), (15360, None), (1000, 10), (7680, 10)])

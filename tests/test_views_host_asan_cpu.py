@@ -109,7 +109,7 @@ def test_view_head_and_flipped_resize_under_asan_ubsan(tmp_path):
     r = subprocess.run([CXX, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-Wno-unused-parameter",
                         "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
                         "-I", os.path.join(ROOT, "csrc", "include"), "-isystem", ROCM_INCLUDE, str(src),
-                        os.path.join(cpu, "ref_layers.cpp"), os.path.join(cpu, "resize_crop_u8.cpp"), "-o", str(exe)],
+                        os.path.join(cpu, "softmax_heads.cpp"), os.path.join(cpu, "resize_crop_u8.cpp"), "-o", str(exe)],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=23")
